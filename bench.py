@@ -10,7 +10,15 @@ One step = one DeterministicEvenOdd PT-MH iteration of every chain on the rank
 run as ONE batched launch of the HIP BDF kernel (bcm3_likelihood_evaluate_batch_device).
 Everything stays in HBM; no host buffers inside the timed region.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+    A plain run sets up, warms up, times the K steps and prints the result line. --dump-outputs DIR
+    also writes the chain state the timed loop leaves after its last step (what a caller of the
+    sampler reads back: values, llh, lprior, lpp) as DIR/<name>.npy, float64; the same arguments
+    give the same inputs, so two builds can be compared output for output. --full adds every
+    secondary measurement to the line (the issue probe, the large batch, the strong-scaling
+    companion, the P=64 / circular / pharmaco / C4 workloads and the CPU baselines); their options
+    below (--cpu-seconds, --throughput-batch, --issue-probe, --extras, --strong-chains) only act
+    under --full.
     N > 1 without a torch.distributed environment: bench.py starts
     `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process (before
     any GPU call) and exits with its code; under torch.distributed.run WORLD_SIZE must equal N.
@@ -55,6 +63,11 @@ def parse():
     ap.add_argument("--speculate", type=int, default=1,
                     help="C++ loop: 1 = speculative iteration pairs (one likelihood launch per two iterations, "
                          "bit-identical chains), 0 = one launch per iteration")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the chain state after the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (issue probe, large batch, strong scaling, other "
+                         "workloads, CPU baselines); without it only the headline is measured")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget (0 = skip)")
     ap.add_argument("--throughput-batch", type=int, default=16384,
                     help="extra: evals/s of one large batch (0 = skip); not the headline value")
@@ -66,7 +79,13 @@ def parse():
                     help="also time this fixed ladder size over all GPUs in the same run (the strong-scaling "
                          "companion of the weak headline, C5 = 2,048; 0 = skip)")
     ap.add_argument("--strong-steps", type=int, default=30, help="timed iterations of the strong-scaling run")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run measures the headline only
+        args.cpu_seconds, args.throughput_batch, args.issue_probe, args.extras, args.strong_chains = 0.0, 0, 0, 0, 0
+    return args
 
 
 def algorithmic_bytes_per_eval(m) -> int:
@@ -148,6 +167,10 @@ class NativeLoop:
         import torch
         return torch.tensor(self.s.state()["values"])
 
+    def outputs(self):
+        """What a caller reads back after iterate(): this rank's chain state (bcm3_ptmh_get_state)."""
+        return self.s.state()
+
 
 class PythonLoop:
     """bcm3_amd.sampler.PTMHDevice (the same iteration written in Python over the same kernels)."""
@@ -174,6 +197,19 @@ class PythonLoop:
 
     def values(self):
         return self.loop.prop
+
+    def outputs(self):
+        lp = self.loop
+        return {k: getattr(lp, k).detach().cpu().numpy() for k in ("values", "llh", "lprior", "lpp")}
+
+
+def dump_outputs(path: str, arrays: dict, rank: int, world: int) -> None:
+    """DIR/<name>.npy per array (one rank) or DIR/<name>_rank<r>.npy (this rank's ladder slice)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(path, f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), a)
 
 
 def spawn_ranks(args) -> int:
@@ -707,6 +743,8 @@ def main():
     k_total, k_launches, k_max = ll.kernel_time_log()
     ll.set_option(_hip.OPT_TIMING_LOG, 0)
     k_avg = k_total / max(1, k_launches)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, loop.outputs(), rank, world)
     rank_k_ms = [k_avg]
     if world > 1:
         t = torch.tensor([dt, k_avg], dtype=torch.float64, device=device)

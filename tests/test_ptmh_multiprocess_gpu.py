@@ -6,8 +6,10 @@ device). With the counter-based random numbers the ladder is bit-identical to on
 process -- including the speculative pairs, whose boundary candidates start from the neighbour
 rank's (state, proposal) rows."""
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -18,6 +20,15 @@ pytestmark = pytest.mark.gpu
 
 WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "workers", "ptmh_rank.py")
 C3 = (os.path.join(H.GOLDEN, "c3_likelihood.xml"), os.path.join(H.GOLDEN, "c3_prior.xml"))
+
+
+@pytest.fixture
+def sock():
+    """The ranks' socket directory. A Unix socket path holds about 100 characters (sun_path), which
+    pytest's tmp_path under a long TMPDIR exceeds, so the directory gets a short name of its own."""
+    d = tempfile.mkdtemp(prefix="bcm3s", dir="/tmp")
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
 
 
 def _single_rank(C, seed, steps):
@@ -33,11 +44,9 @@ def _single_rank(C, seed, steps):
 
 
 @pytest.mark.parametrize("speculate", [1, 0])
-def test_two_processes_bit_identical_to_one_rank(tmp_path, speculate):
+def test_two_processes_bit_identical_to_one_rank(tmp_path, sock, speculate):
     C, seed, steps, world = 32, 17, 61, 2
     ref, cref = _single_rank(C, seed, steps)
-    sock = str(tmp_path / "s")
-    os.makedirs(sock)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     procs = [subprocess.Popen([sys.executable, WORKER, str(tmp_path / f"rank{r}.npz"), sock, str(r), str(world), str(C),
                                str(seed), str(steps), str(speculate)], env=env, stdout=subprocess.PIPE,
@@ -59,7 +68,7 @@ def test_two_processes_bit_identical_to_one_rank(tmp_path, speculate):
     assert sum(int(g["accepted_mutate"]) for g in got) == cref["accepted_mutate"]
 
 
-def test_two_processes_netcdf4_output_is_the_one_rank_file(tmp_path, monkeypatch):
+def test_two_processes_netcdf4_output_is_the_one_rank_file(tmp_path, sock, monkeypatch):
     """a sharded ladder writes the reference's netCDF-4 output.nc
     (SampleHandlerNetCDF.cpp:24-110) -- rank 0 receives the other ranks' staged sample rows over the
     transport at each flush and writes every temperature; through the libnetcdf test double
@@ -78,8 +87,6 @@ def test_two_processes_netcdf4_output_is_the_one_rank_file(tmp_path, monkeypatch
     s.flush_output()
     s.close()
     sharded = str(tmp_path / "sharded.nc")
-    sock = str(tmp_path / "s")
-    os.makedirs(sock)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     procs = [subprocess.Popen([sys.executable, WORKER, str(tmp_path / f"rank{r}.npz"), sock, str(r), str(world), str(C),
                                str(seed), str(steps), "0", sharded], env=env, stdout=subprocess.PIPE,

@@ -17,14 +17,17 @@ import helpers as H
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 RB = os.path.join(HERE, "refbind")
-DRIVER = os.path.join(RB, "build", "refbind_driver")
 ROOT = os.path.dirname(HERE)
+# compiled against the reference's vendored Eigen headers, so it is kept with the other reference
+# builds in oracle/_ref (oracle/Makefile, target ref)
+DRIVER = os.path.join(ROOT, "oracle", "_ref", "refbind_driver")
 
 
 def _driver():
     if not os.path.exists(DRIVER):
         # built by __graft_entry__.build() (needs the reference's vendored Eigen headers)
-        subprocess.run(["make", "-C", RB], check=True, capture_output=True)
+        subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "_ref/refbind_driver"], check=True,
+                       capture_output=True)
     return DRIVER
 
 

@@ -21,7 +21,7 @@ if [ -z "$NOTESTS" ]; then
   tail -1 $O/smoke.log
 fi
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err
+  timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err
   head -c 1500 $O/bench.json
 fi
 if [ -n "$VARIANTS" ]; then
