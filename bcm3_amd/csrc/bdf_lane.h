@@ -21,9 +21,9 @@
 //    1..QMAX with per-j guards on q. No inline-asm barriers: with one trajectory per wavefront
 //    (UNI launch) every value stays wave-uniform to the compiler and every solver branch is a
 //    scalar branch;
-//  * division / sqrt / x^(1/k) use hardware reciprocal + one Newton refinement (within ~11 ulp;
-//    correctly rounded with -DBCM3_CORRECTLY_ROUNDED), a perturbation well inside the
-//    reference's own FMA-contraction build differences -- see DESIGN.md "parity envelope";
+//  * division and sqrt are the hardware estimate refined to the correctly rounded (IEEE) result
+//    (frcp / fdiv / fsqrt below); x^(1/k) is glibc's pow (pow_root) in the PopPK solvers and a
+//    Newton root (eta_from) in the cell-population solver -- see DESIGN.md "parity envelope";
 //  * the model supplies a structured (I - gamma J) inverse: for constant-Jacobian models the
 //    saved Jacobian of cvLsLinSys is re-derived from the parameters instead of stored.
 #pragma once
@@ -74,31 +74,10 @@ enum { CV_SUCCESS = 0, CV_TSTOP_RETURN = 1, CV_TOO_MUCH_ACC = -2, CV_ERR_FAILURE
        CV_CONV_FAILURE = -4, CV_ILL_INPUT = -22, CV_BAD_T = -26, CV_TOO_CLOSE = -27 };
 
 #define BDF_INL __device__ __forceinline__
-// BCM3_DBL=k (cost-probe builds only, tools/dbl_probe.sh): component k of the step runs twice, the
-// second time on operands laundered through an empty asm and with its results consumed by one, so
-// the solve's results are unchanged and the kernel time grows by what that component costs
-// (1 step-size root, 2 order-change screen, 3 exact order-change evaluation, 4 cvSet coefficients,
-// 5 Newton correction, 6 linear-solver setup, 7 error weights, 8 fast-loop exit test, 9 predict)
-#ifdef BCM3_DBL
-#define BDF_DBL(k) (BCM3_DBL == (k))
-#else
-#define BDF_DBL(k) false
-#endif
-BDF_INL double bdf_launder(double x)
-{
-    asm volatile("" : "+v"(x));
-    return x;
-}
-BDF_INL void bdf_consume(double x) { asm volatile("" ::"v"(x)); }
 
 // branch-layout hints for the UNI solver (hot path falls through; rare work out of line)
-#ifdef BCM3_NO_EXPECT
-#define BDF_LIKELY(x) (x)
-#define BDF_UNLIKELY(x) (x)
-#else
 #define BDF_LIKELY(x) __builtin_expect(!!(x), 1)
 #define BDF_UNLIKELY(x) __builtin_expect(!!(x), 0)
-#endif
 
 // readfirstlane of both halves: the value is (already) the same in every lane, or only lane 0's
 // value is wanted; the result is uniform to the compiler
@@ -136,83 +115,55 @@ BDF_INL void cfor_down(F&& f)
 #define SUNMIN(A, B) ((A) < (B) ? (A) : (B))
 
 // ---------------------------------------------------------------------------------------------
-// Fast arithmetic for the divisions, reciprocals and square roots of the BDF step. By default
-// v_rcp_f64 / v_rsq_f64 with ONE Newton (Goldschmidt) step: within ~11 ulp (tools/ubench/
-// rcp_acc.hip, sqrt_acc.hip), 5 % faster per launch at 256 draws (1.425 vs 1.505 ms, C3) and 9 %
-// at 2048 than the correctly rounded forms, which -DBCM3_CORRECTLY_ROUNDED restores (one more
-// Newton step / a residual correction; identical to the CPU's IEEE results on 4M random
-// operands). Either way the three solver forms share these functions and agree bit for bit
-// (tools/lane_diff.py); a divisor that is a compile-time constant in the order-specialised forms
-// but not in the lane form must go through fdiv_c with its folded reciprocal (tq_ra3) or a runtime
-// 1.0 (BdfState::unity), since the compiler folds v_rcp_f64 of a constant to the correctly rounded
-// value. The GPU-vs-CPU llh parity envelope (tests/parity.py) holds for both (512 C3 draws:
-// 99.6 % within 1e-8 fast, 99.4 % correctly rounded).
+// The divisions, reciprocals and square roots of the BDF step, correctly rounded: v_rcp_f64 /
+// v_rsq_f64, Newton (Goldschmidt) refinement and a residual correction give the reference's IEEE
+// results (identical to the CPU's on 4M random operands; tools/ubench/rcp_acc.hip, sqrt_acc.hip).
+// The three solver forms share these functions and agree bit for bit (tools/lane_diff.py); a
+// divisor that is a compile-time constant in the order-specialised forms but not in the lane form
+// must go through fdiv_c with its folded reciprocal (tq_ra3) or a runtime 1.0 (BdfState::unity),
+// since the compiler folds v_rcp_f64 of a constant to the correctly rounded value.
 
-// Default (round 3): the correctly rounded forms -- the reference's IEEE quotients, and the GPU's
-// llh agreement with the reference CVODE then meets the reference's own FMA on/off spread (4,096
-// C3 draws: 99.05 % within 1e-8 vs 98.88 % with the one-step forms; profiles/r03_parity_variants.txt).
-// -DBCM3_FAST_DIV selects the one-Newton-step forms (tools/build_variant.sh).
-#if !defined(BCM3_FAST_DIV) && !defined(BCM3_CORRECTLY_ROUNDED)
-#define BCM3_CORRECTLY_ROUNDED
-#endif
-
-// reciprocal
+// reciprocal: two Newton steps on the hardware estimate
 BDF_INL double frcp(double b)
 {
     double r = __builtin_amdgcn_rcp(b);
     double e = __builtin_fma(-b, r, 1.0);
     r = __builtin_fma(e, r, r);
-#ifndef BCM3_CORRECTLY_ROUNDED
-    return r;
-#else
     e = __builtin_fma(-b, r, 1.0);
     return __builtin_fma(e, r, r);
-#endif
 }
-// a / b: a times the one-step reciprocal (correctly rounded: + one residual correction of the
-// quotient)
+// a / b: a times the one-step reciprocal + one residual correction of the quotient
 BDF_INL double fdiv(double a, double b)
 {
     double r = __builtin_amdgcn_rcp(b);
     const double e0 = __builtin_fma(-b, r, 1.0);
     r = __builtin_fma(e0, r, r);
     const double q = a * r;
-#ifndef BCM3_CORRECTLY_ROUNDED
-    return q;
-#else
     const double e = __builtin_fma(-b, q, a);
     return __builtin_fma(e, r, q);
-#endif
 }
-// SUNRsqrt: x <= 0 -> 0; v_rsq_f64 estimate + one Goldschmidt step (correctly rounded: + one
-// correction). Branch-free: the refinement runs for every x (x <= 0 gives NaN there) and x <= 0
-// is zeroed with a bit mask, NaN passes through (a select here is turned back into a branch by
-// the compiler).
+// SUNRsqrt: x <= 0 -> 0; v_rsq_f64 estimate + one Goldschmidt step + one correction. Branch-free:
+// the refinement runs for every x (x <= 0 gives NaN there) and x <= 0 is zeroed with a bit mask,
+// NaN passes through (a select here is turned back into a branch by the compiler).
 BDF_INL double fsqrt(double x)
 {
     double r = __builtin_amdgcn_rsq(x);
     double g = x * r, hh = 0.5 * r;
     double e = __builtin_fma(-g, hh, 0.5);
     g = __builtin_fma(g, e, g);
-#ifdef BCM3_CORRECTLY_ROUNDED
     hh = __builtin_fma(hh, e, hh);
     const double d = __builtin_fma(-g, g, x);
     g = __builtin_fma(d, hh, g);
-#endif
     const long long keep = (x <= 0.0) ? 0LL : -1LL;
     return __builtin_bit_cast(double, __builtin_bit_cast(long long, g) & keep);
 }
-// a / b for a compile-time b with rb = 1/b correctly rounded: a * rb (correctly rounded: + the
-// residual correction of fdiv)
+// a / b for a compile-time b with rb = 1/b correctly rounded: a * rb + the residual correction
+// of fdiv
 BDF_INL double fdiv_c(double a, double b, double rb)
 {
     const double q = a * rb;
-#ifndef BCM3_CORRECTLY_ROUNDED
-    return q;
-#else
     const double e = __builtin_fma(-b, q, a);
     return __builtin_fma(e, rb, q);
-#endif
 }
 
 // 1/j for j = 1..7 (the correctly rounded quotients 1.0/j)
@@ -282,50 +233,12 @@ BDF_INL double eta_from(double bx, int k)
 // SUNRpowerR(bx, fl(1/k)) (sundials_math.c:40-52, libm's pow)
 // with the tables popk_prepare_device uploaded (xm::xm_tables: the host libm's own, so that the
 // roots are glibc's results bit for bit, or computed ones of the same layout, ~1 ulp)
-#ifdef BCM3_TABLES_LDS
-// (variant) a workgroup copy of the tables in LDS, filled at kernel entry (popk_traj_kernel)
-static __shared__ xm::GlibcPow lds_tables;
-#define BDF_ROOT_TABLES lds_tables
-#else
-#define BDF_ROOT_TABLES xm::xm_tables
-#endif
-// SUNRpowerR's pow: glibc's table-driven pow (the tables popk_prepare_device uploaded). Measured
-// against the alternatives on one box (profiles/r04n_variants.txt, 256 C3 draws): the correctly
-// rounded Newton root alone is 6 % faster but not glibc's result on ~0.07 % of roots; checking it
-// against the rounding midpoints and falling back to glibc's pow near them (BCM3_ROOT_HYBRID,
-// xm::pow_inv_k_checked) is glibc's result everywhere but 4 % slower than this -- two root code
-// paths inlined at every call site cost more than the table loads.
-#ifdef BCM3_ROOT_CALL
-__device__ __attribute__((noinline)) double pow_glibc_call(double bx, int k)
-{
-    return xm::pow_glibc(bx, xm::inv_k(k), BDF_ROOT_TABLES);
-}
-#endif
+// SUNRpowerR's pow: glibc's table-driven pow. The Newton root (xm::pow_inv_k) is faster but not
+// glibc's result on ~0.07 % of roots (profiles/r04n_variants.txt); it serves only without tables.
 BDF_INL double pow_root(double bx, int k)
 {
-#ifdef BCM3_ROOT_LEAN
-    // the tables are always uploaded before a launch (popk_prepare_device: the loaded libm's, else
-    // computed ones of the same layout, ok = 1 either way), so every finite bx > 0 takes glibc's
-    // algorithm (subnormal bx normalised as e_pow.c does); SUNRpowerR's base <= 0 -> 0 and pow's
-    // inf -> inf, NaN -> NaN by selects: one straight-line copy per call site
-    const bool fin = (bx > 0.0) & (bx < __builtin_inf());
-    const double p = xm::pow_glibc_pos(fin ? bx : 1.0, xm::inv_k(k), BDF_ROOT_TABLES);
-    return fin ? p : ((bx > 0.0) ? bx : ((bx == bx) ? 0.0 : bx + bx));
-#endif
-#if defined(BCM3_ROOT_HYBRID) || defined(BCM3_ROOT_CALL) || defined(BCM3_ROOT_CR)
-    if (BDF_LIKELY((bx > 1e-30) & (bx < 1e30))) {
-        bool safe;
-        const double p = xm::pow_inv_k_checked(bx, k, safe);
-#if defined(BCM3_ROOT_CALL)
-        if (BDF_UNLIKELY(!safe & (BDF_ROOT_TABLES.ok != 0))) return pow_glibc_call(bx, k);
-#elif defined(BCM3_ROOT_HYBRID)
-        if (BDF_UNLIKELY(!safe & (BDF_ROOT_TABLES.ok != 0))) return xm::pow_glibc(bx, xm::inv_k(k), BDF_ROOT_TABLES);
-#endif
-        return p;
-    }
-#endif
-    if (BDF_LIKELY(BDF_ROOT_TABLES.ok & (bx >= 0x1p-1022) & (bx < 0x1p1023)))
-        return xm::pow_glibc(bx, xm::inv_k(k), BDF_ROOT_TABLES);
+    if (BDF_LIKELY(xm::xm_tables.ok & (bx >= 0x1p-1022) & (bx < 0x1p1023)))
+        return xm::pow_glibc(bx, xm::inv_k(k), xm::xm_tables);
     if (bx > 1e-30 && bx < 1e30) return xm::pow_inv_k(bx, k);
     return (bx > 0.0) ? pow(bx, xm::inv_k(k)) : 0.0;
 }
@@ -334,7 +247,6 @@ BDF_INL double pow_root(double bx, int k)
 // exponent fl(1/k) as the reference passes it, libm's pow, the IEEE quotient
 BDF_INL double eta_exact(double bx, int k)
 {
-    if constexpr (BDF_DBL(1)) bdf_consume(frcp(pow_root(bdf_launder(bx), k) + ADDON));
     return frcp(pow_root(bx, k) + ADDON);
 }
 

@@ -28,11 +28,7 @@
 // hot loop. lib<COLD> picks one at a call site: the one-trajectory-per-wavefront PopPK kernel with
 // vector state calls them out of line; the other kernels inline them (a call from the scalar-state
 // two-compartment transit kernel was miscompiled: every solve failed on its first step)
-#ifdef BCM3_XM_INLINE
-#define XM_COLD XM_FN
-#else
 #define XM_COLD __host__ __device__ __attribute__((noinline)) inline
-#endif
 #else
 #include <cmath>
 #define XM_FN inline
@@ -383,9 +379,7 @@ XM_FN double pow_glibc_ix(unsigned long long ix, double y, const GlibcPow& D)
     const double ehi = y * ly;
     const double elo = __builtin_fma(y, ltail, __builtin_fma(ly, y, -ehi));
     const int abstop = (int)((as_bits(ehi) >> 52) & 0x7ff);
-#ifndef BCM3_ROOT_LEAN
     if (abstop < 0x3c9) return 1.0 + ehi;  // |y log x| < 2^-54
-#endif
     // exp_inline: ehi = (k + i/128) ln2 + r, 2^(i/128) from the table, exp(r) by its polynomial
     const double kz = __builtin_fma(ehi, D.invln2N, D.shift);
     const unsigned long long ki = (unsigned long long)as_bits(kz);
@@ -403,12 +397,7 @@ XM_FN double pow_glibc_ix(unsigned long long ix, double y, const GlibcPow& D)
     const double s1 = __builtin_fma(c23, r2, tr);
     const double t = __builtin_fma(c45, r2 * r2, s1);
     const double scale = as_double((long long)sbits);
-#ifdef BCM3_ROOT_LEAN
-    // (the tiny case as a select: the exp path's operands are finite there too)
-    return (abstop < 0x3c9) ? 1.0 + ehi : __builtin_fma(t, scale, scale);  // |y log x| < 2^-54
-#else
     return __builtin_fma(t, scale, scale);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -249,25 +249,6 @@ BDF_INL bool check_give_treatment(double t, const uint8_t* skipped, int intermit
 // state vectors across lanes: bdf_vec.h). All three give the same bits.
 enum { POPK_LANES = 0, POPK_UNI = 1, POPK_VEC = 2 };
 
-// the kernel's argument list as a struct: the byte offsets of its members are those of the kernarg
-// segment (the code object's .args metadata: logp_direct at 216 ... place_out at 272)
-struct PopkArgsLayout {
-    PopPKDevModel m;
-    int64_t ntraj;
-    int lpw;
-    const double* values;
-    double* logp_direct;
-    double* patient_llh;
-    int32_t* traj_status;
-    double* traj_out;
-    bcm3hip_traj_stats* stats_out;
-    const int32_t* n_dev;
-    int32_t* steps_out;
-    uint64_t* place_out;
-};
-static_assert(offsetof(PopkArgsLayout, logp_direct) == 216 && offsetof(PopkArgsLayout, place_out) == 272,
-              "popk_traj_kernel's kernarg layout changed: re-check the code object's .args offsets");
-
 template <int PKT, int MODE, bool STATS>
 __global__ void __launch_bounds__(256) popk_traj_kernel(PopPKDevModel m, int64_t ntraj, int lpw,
                                                         const double* __restrict__ values,
@@ -285,24 +266,9 @@ __global__ void __launch_bounds__(256) popk_traj_kernel(PopPKDevModel m, int64_t
     constexpr bool UNI = (MODE != POPK_LANES);
     constexpr bool VEC = (MODE == POPK_VEC);
     // library functions out of line (libm_exact.h xm::lib) in both one-trajectory-per-wavefront
-    // kernels. Round 6 closed the round-4 question: the scalar-state kernel built this way under the
-    // product's flags is bit-identical to the inlining build on all 6 PK models x 7 dosing rules x 3
-    // solver forms (tools/flag_diff.py, profiles/r06e_flag_diff.txt), so the inline workaround is
-    // dropped; BCM3_UNI_INLINE restores it for diagnostics
-#ifdef BCM3_UNI_INLINE
-    constexpr bool COLD = VEC;
-#else
+    // kernels (bit-identical to inlining them: tools/flag_diff.py)
     constexpr bool COLD = UNI;
-#endif
     const int lane = threadIdx.x & 63;
-#ifdef BCM3_TABLES_LDS
-    {
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(&xm::xm_tables);
-        unsigned long long* dst = reinterpret_cast<unsigned long long*>(&lds_tables);
-        for (int i = threadIdx.x; i < (int)(sizeof(xm::GlibcPow) / 8); i += blockDim.x) dst[i] = src[i];
-        __syncthreads();
-    }
-#endif
     // n_dev: the number of evaluations is a device value (the speculative batches of the sampler
     // size themselves on the device); the grid covers the maximum and the rest return here
     if (n_dev) ntraj = (int64_t)__builtin_amdgcn_readfirstlane(*n_dev) * m.P;
@@ -497,23 +463,9 @@ __global__ void __launch_bounds__(256) popk_traj_kernel(PopPKDevModel m, int64_t
             s.tstopset = 1;
             int current_step = 0;
             bool hot = false;  // previous step was a plain CV_SUCCESS (uni::cvode_one_step_u)
-#ifdef BCM3_PRIO_STEPS
-            int prio_level = 0;
-#endif
             for (;;) {
                 double tret = 0.0;
                 int result;
-#ifdef BCM3_PRIO_STEPS
-                // (variant) a trajectory that has run long gets the higher issue priority on a shared
-                // SIMD (s_setprio; the launch waits for its longest trajectory): checked once per
-                // return to this loop
-                if (BDF_UNLIKELY(current_step >= BCM3_PRIO_STEPS * (prio_level + 1) && prio_level < 3)) {
-                    prio_level++;
-                    if (prio_level == 1) __builtin_amdgcn_s_setprio(1);
-                    else if (prio_level == 2) __builtin_amdgcn_s_setprio(2);
-                    else __builtin_amdgcn_s_setprio(3);
-                }
-#endif
                 if constexpr (VEC) {
                     // after a plain step: run the following plain steps in vec::fast_run (same
                     // results, one exit test per step); an order change the last step decided is
@@ -635,21 +587,6 @@ __global__ void __launch_bounds__(256) popk_traj_kernel(PopPKDevModel m, int64_t
     if (tro) cfor<0, NPHASES>([&](auto k) __attribute__((always_inline)) { tro[CI(k)] = (double)s.ph[CI(k)]; });
     if (tro) cfor<1, QMAX + 1>([&](auto k) __attribute__((always_inline)) { tro[NPHASES + CI(k) - 1] = (double)s.qh[CI(k)]; });
 #endif
-#ifdef BCM3_LATE_ARGS
-    {
-        // (variant) the output pointers read from the kernarg segment only now, through a laundered
-        // segment pointer, so that none of them holds scalar registers through the solve
-        const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(ka));
-        const PopkArgsLayout* A = reinterpret_cast<const PopkArgsLayout*>(ka);
-        logp_direct = A->logp_direct;
-        patient_llh = A->patient_llh;
-        traj_status = A->traj_status;
-        stats_out = A->stats_out;
-        steps_out = A->steps_out;
-        place_out = A->place_out;
-    }
-#endif
     // one lane stores a wave-uniform trajectory's results (UNI / VEC: every lane holds the same
     // values; 64 same-address stores were 375 B of write traffic per trajectory)
     const bool writer = !UNI || lane == 0;
@@ -752,13 +689,8 @@ hipError_t launch_popk(const PopPKDevModel& m, int64_t n, const double* values, 
     // one patient: the trajectory status is the evaluation status, written in place (no copy kernel)
     int32_t* tstat = (direct && status) ? status : traj_status_scratch;
     if (ev_start) hipEventRecord(ev_start, stream);
-#ifdef BCM3_VEC_STATS_ALWAYS
-    constexpr bool vec_nostats = false;  // (variant) the counting kernel for every vector-state launch
-#else
-    constexpr bool vec_nostats = true;
-#endif
 #define LAUNCH(PKT)                                                                                           \
-    if (vec_state && !stats_out && vec_nostats)                                                               \
+    if (vec_state && !stats_out)                                                                              \
         hipLaunchKernelGGL((popk_traj_kernel<PKT, POPK_VEC, false>), grid, block, block_lds, stream, m, ntraj, lpw,     \
                            values, logp_direct, patient_llh_scratch, tstat, traj_out, nullptr, n_dev, steps_out, place_out); \
     else if (vec_state)                                                                                       \
@@ -773,7 +705,7 @@ hipError_t launch_popk(const PopPKDevModel& m, int64_t n, const double* values, 
 #ifdef BCM3_DEV_TWO_VEC
     // development build (tools/resource_two_vec.sh): only the C3 kernel, compiled in seconds
     if (m.pk_type != BCM3HIP_PK_TWO || !vec_state || stats_out) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((popk_traj_kernel<BCM3HIP_PK_TWO, POPK_VEC, !vec_nostats>), grid, block, block_lds, stream, m, ntraj,
+    hipLaunchKernelGGL((popk_traj_kernel<BCM3HIP_PK_TWO, POPK_VEC, false>), grid, block, block_lds, stream, m, ntraj,
                        lpw, values, logp_direct, patient_llh_scratch, tstat, traj_out, nullptr, n_dev, steps_out, place_out);
 #else
     switch (m.pk_type) {

@@ -46,7 +46,7 @@ def main():
     src = sys.argv[1] if len(sys.argv) > 1 else "/tmp/cp_model.hip"
     asm = "/tmp/cp_isa_stats.s"
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S",
-                    "-ffp-contract=off", "-DBCM3_CORRECTLY_ROUNDED", "-I" + os.path.join(ROOT, "bcm3_amd", "csrc"), "-w",
+                    "-ffp-contract=off", "-I" + os.path.join(ROOT, "bcm3_amd", "csrc"), "-w",
                     "-o", asm, src], check=True)
     lines = open(asm).read().split("\n")
     kernel = sys.argv[2] if len(sys.argv) > 2 else "cp_solve_kernel"
