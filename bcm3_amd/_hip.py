@@ -85,6 +85,12 @@ class Proposal(C.Structure):
                                           "ema", "selected", "work")]
 
 
+class Blocks(C.Structure):
+    """bcm3hip_blocks (device pointers): per-chain block tables and the per-block proposal state"""
+    _fields_ = [(k, C.c_void_p) for k in ("nblocks", "block_offset", "block_vars", "target", "ncomp", "selected",
+                                          "weights", "logc", "scale", "ema", "mean", "chol", "active")]
+
+
 STATS_DTYPE = np.dtype([(k, np.int32) for k in ("nst", "nfe", "nni", "nsetups", "nje", "netf", "ncfn", "nreinit")])
 
 _lib = None
@@ -127,6 +133,11 @@ def lib() -> C.CDLL:
                                                 C.POINTER(Proposal), i64, u64, u64, vp]
     L.bcm3hip_ptmh_accept_adaptive.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp,
                                                vp, vp, vp, C.POINTER(Proposal), i64, u64, u64, vp]
+    L.bcm3hip_ptmh_propose_blocked.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                               C.POINTER(Proposal), C.POINTER(Blocks), i64, u64, u64, vp]
+    L.bcm3hip_ptmh_accept_blocked.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp,
+                                              vp, vp, vp, vp, C.POINTER(Proposal), C.POINTER(Blocks), i64, u64, u64,
+                                              vp]
     L.bcm3hip_pt_exchange_pair.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, i64, vp, vp, vp, vp, vp, vp, vp,
                                            u64, u64, vp]
     L.bcm3hip_history_add.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
@@ -357,6 +368,24 @@ def ptmh_accept_adaptive(C, d, temps, prop, lprior_prop, llh_prop, log_mh, learn
     check(lib().bcm3hip_ptmh_accept_adaptive(C, d, temps, prop, lprior_prop, llh_prop, log_mh, learning_rate, values,
                                              lprior, llh, lpp, accept_out, accepted, nan_llh, C_byref(proposal),
                                              chain0, _u64(seed), _u64(it), stream), "ptmh_accept_adaptive")
+
+
+def ptmh_propose_blocked(C, d, submove, kind, p0, p1, p2, temps, values, prop, lprior_prop, log_mh,
+                         proposal: Proposal, blocks: Blocks, chain0, seed, it, stream=None):
+    """bcm3hip_ptmh_propose_blocked on device pointers (ints), a Proposal and a Blocks of device pointers."""
+    check(lib().bcm3hip_ptmh_propose_blocked(C, d, submove, kind, p0, p1, p2, temps, values, prop, lprior_prop,
+                                             log_mh, C_byref(proposal), C_byref(blocks), chain0, _u64(seed),
+                                             _u64(it), stream), "ptmh_propose_blocked")
+
+
+def ptmh_accept_blocked(C, d, submove, temps, prop, lprior_prop, llh_prop, log_mh, learning_rate, values, lprior, llh,
+                        lpp, accept_out, accepted, proposal: Proposal, blocks: Blocks, chain0, seed, it, stream=None,
+                        nan_llh=None):
+    """bcm3hip_ptmh_accept_blocked on device pointers (ints; accept_out / accepted / nan_llh may be None)."""
+    check(lib().bcm3hip_ptmh_accept_blocked(C, d, submove, temps, prop, lprior_prop, llh_prop, log_mh, learning_rate,
+                                            values, lprior, llh, lpp, accept_out, accepted, nan_llh,
+                                            C_byref(proposal), C_byref(blocks), chain0, _u64(seed), _u64(it),
+                                            stream), "ptmh_accept_blocked")
 
 
 def pt_exchange_pair(C, d, i1, i2, g1, temps, values, llh, lprior, lpp, acc_out, accepted, seed, rnd, stream=None):

@@ -270,8 +270,14 @@ bool LoadRunConfig(const std::string& path, RunConfig& out)
 
     // SamplerPT::LoadSettings (SamplerPT.cpp:40-95)
     const std::string blocking = cf.String("ptmhsampler.blocking_strategy");
-    if (blocking != "one_block") {
-        LOGERROR("ptmhsampler.blocking_strategy \"%s\": only one_block is built (DESIGN.md §8)", blocking.c_str());
+    if (blocking == "one_block") {
+        p.blocking = BCM3_PTMH_ONE_BLOCK;
+    } else if (blocking == "no_blocking") {
+        p.blocking = BCM3_PTMH_NO_BLOCKING;
+    } else {
+        // Turek / clustered_autoblock (SamplerPTChain.cpp:66-77) need a clustering of the history
+        LOGERROR("ptmhsampler.blocking_strategy \"%s\": only one_block and no_blocking are built (DESIGN.md §8)",
+                 blocking.c_str());
         return false;
     }
     if (cf.Bool("ptmhsampler.proposal_transform_to_unbounded")) {

@@ -263,6 +263,17 @@ struct SamplerPTDevice::Impl {
     PTMHCounters cnt;
     int64_t iter = 0, round = 0;
 
+    // variable blocks (cfg.blocking != one_block): the tables of the rank's chains on the host, the
+    // per-block proposal state in HBM, and per sub-move the accept decisions it takes
+    bool blocked = false;
+    int max_blocks = 1;
+    std::vector<int32_t> bl_n, bl_off, bl_vars;
+    std::vector<int64_t> sub_decisions;
+    DevBuf<int32_t> b_nblocks, b_offset, b_vars, b_ncomp, b_selected;
+    DevBuf<double> b_target, b_weights, b_logc, b_scale, b_ema, b_mean, b_chol;
+    DevBuf<uint8_t> b_active;
+    bcm3hip_blocks B{};
+
     // speculative iteration pairs (bcm3hip_ptmh_spec_*): candidate / batch buffers, per round parity
     // the exchange partner and the first chain of each chain's pair, accept flags of both moves
     bool spec_on = false;
@@ -502,6 +513,199 @@ struct SamplerPTDevice::Impl {
                              bcm3hip_memset_async(sp_batch_n.p, 0, sizeof(int32_t), stream) == 0));
     }
 
+    // ---- variable blocks (cfg.blocking != one_block): per-block proposal state (bcm3hip_blocks) ----
+
+    // offset / size / variables of block b of chain c
+    int BlockOffset(int64_t c, int b) const { return bl_off[(size_t)(c * (d + 1) + b)]; }
+    int BlockSize(int64_t c, int b) const { return BlockOffset(c, b + 1) - BlockOffset(c, b); }
+    const int32_t* BlockVars(int64_t c, int b) const { return &bl_vars[(size_t)(c * d + BlockOffset(c, b))]; }
+
+    // the table from the blocking strategy, the same for every chain of the rank (a strategy that
+    // clusters each chain's history would fill the per-chain rows differently), and the prior-moment
+    // proposal of every block: the reference adapts once on an empty history in
+    // SamplerPTChain::Initialize (SamplerPTChain.cpp:95), which is InitProposal's state per block
+    bool SetupBlocks()
+    {
+        if (!adaptive || d > 64) {
+            LOGERROR("SamplerPTDevice: variable blocks need an adaptive proposal and at most 64 variables (%d)", d);
+            return false;
+        }
+        if (cfg.blocking == BCM3_PTMH_EXPLICIT_BLOCKS && (int)cfg.block_of_variable.size() != d) {
+            LOGERROR("SamplerPTDevice: block_of_variable has %zu entries for %d variables", cfg.block_of_variable.size(), d);
+            return false;
+        }
+        int32_t nb = 0;
+        std::vector<int32_t> off(d + 1), vars(d);
+        if (bcm3_build_blocks(cfg.blocking, d, cfg.blocking == BCM3_PTMH_EXPLICIT_BLOCKS ? cfg.block_of_variable.data() : nullptr,
+                              &nb, off.data(), vars.data()) != 0)
+            return false;
+        bl_n.assign(C, nb);
+        bl_off.resize(C * (d + 1));
+        bl_vars.resize(C * d);
+        for (int64_t c = 0; c < C; c++) {
+            std::copy(off.begin(), off.end(), bl_off.begin() + c * (d + 1));
+            std::copy(vars.begin(), vars.end(), bl_vars.begin() + c * d);
+        }
+        max_blocks = nb;
+        sub_decisions.assign(max_blocks, 0);
+        for (int m = 0; m < max_blocks; m++)
+            for (int64_t c = 0; c < C; c++)
+                if (temps_host[c] == 0.0 ? m == 0 : m < bl_n[c]) sub_decisions[m]++;
+        const int64_t K = kmax;
+        if (!b_nblocks.alloc(C) || !b_offset.alloc(C * (d + 1)) || !b_vars.alloc(C * d) || !b_target.alloc(C * d) ||
+            !b_ncomp.alloc(C * d) || !b_selected.alloc(C * d) || !b_weights.alloc(C * d * K) ||
+            !b_logc.alloc(C * d * K) || !b_scale.alloc(C * d * K) || !b_ema.alloc(C * d * K) ||
+            !b_mean.alloc(C * K * d) || !b_chol.alloc(C * K * d * d) || !b_active.alloc(C)) {
+            LOGERROR("SamplerPTDevice: device allocation failed (variable blocks)");
+            return false;
+        }
+        B.nblocks = b_nblocks.p;
+        B.block_offset = b_offset.p;
+        B.block_vars = b_vars.p;
+        B.target = b_target.p;
+        B.ncomp = b_ncomp.p;
+        B.selected = b_selected.p;
+        B.weights = b_weights.p;
+        B.logc = b_logc.p;
+        B.scale = b_scale.p;
+        B.ema = b_ema.p;
+        B.mean = b_mean.p;
+        B.chol = b_chol.p;
+        B.active = b_active.p;
+        std::vector<int32_t> nc(C * d, 1), sel(C * d, -1);
+        std::vector<double> tg(C * d, 0.234), w(C * d * K, 0.0), lc(C * d * K, 0.0), sc(C * d * K, 1.0),
+            em(C * d * K, 0.23), mu(C * K * d, 0.0), L(C * K * d * d, 0.0);
+        const bool gmm = kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE;
+        for (int64_t c = 0; c < C; c++)
+            for (int b = 0; b < bl_n[c]; b++) {
+                const int o = BlockOffset(c, b), s = BlockSize(c, b);
+                const int32_t* v = BlockVars(c, b);
+                const int64_t cb = c * d + b;
+                // Proposal::Initialize (Proposal.cpp:45-53) with the block's size
+                tg[cb] = (s == 1) ? 0.44 : (s == 2) ? 0.35 : (s == 3) ? 0.3 : 0.234;
+                double det = 0.0;
+                for (int j = 0; j < s; j++) det += std::log(std::sqrt(prior_var[v[j]]));
+                w[cb * K] = 1.0;
+                double* m0 = &mu[(size_t)(c * K * d + K * o)];
+                double* L0 = &L[(size_t)(c * K * d * d + K * o * d)];
+                for (int j = 0; j < s; j++) m0[j] = prior_mean[v[j]];
+                for (int k = 0; k < K; k++) {
+                    for (int j = 0; j < s; j++) L0[(size_t)k * s * s + j * s + j] = (k == 0) ? std::sqrt(prior_var[v[j]]) : 1.0;
+                    lc[cb * K + k] = ((k == 0) ? -det : -0.0) - 0.5 * s * std::log(2.0 * M_PI);
+                    sc[cb * K + k] = gmm ? 2.38 / std::sqrt((double)s) : 1.0;
+                    em[cb * K + k] = gmm ? tg[cb] : 0.23;
+                }
+            }
+        return Upload(b_nblocks, bl_n, stream) && Upload(b_offset, bl_off, stream) && Upload(b_vars, bl_vars, stream) &&
+               Upload(b_target, tg, stream) && Upload(b_ncomp, nc, stream) && Upload(b_selected, sel, stream) &&
+               Upload(b_weights, w, stream) && Upload(b_logc, lc, stream) && Upload(b_scale, sc, stream) &&
+               Upload(b_ema, em, stream) && Upload(b_mean, mu, stream) && Upload(b_chol, L, stream) &&
+               bcm3hip_memset_async(b_active.p, 0, C, stream) == 0;
+    }
+
+    // MutateMove's loop over blocks (SamplerPTChain.cpp:249-307): per sub-move every chain's block
+    // proposal, one batched likelihood launch, the accepts; then one history add (:309). The host
+    // knows the number of sub-moves from the table, so nothing synchronises
+    bool MutateBlocked()
+    {
+        for (int m = 0; m < max_blocks; m++) {
+            if (!Launch(bcm3hip_ptmh_propose_blocked((int)C, d, m, pkind.p, p0.p, p1.p, p2.p, temps.p, values.p, prop.p,
+                                                     lprior_prop.p, log_mh.p, &P, &B, g0, cfg.seed, (uint64_t)iter,
+                                                     stream),
+                        "ptmh_propose_blocked") ||
+                !Eval(prop.p, llh_prop.p) ||
+                !Launch(bcm3hip_ptmh_accept_blocked((int)C, d, m, temps.p, prop.p, lprior_prop.p, llh_prop.p, log_mh.p,
+                                                    cfg.learning_rate, values.p, lprior.p, llh.p, lpp.p, nullptr,
+                                                    acc_mutate.p, nan_flag.p, &P, &B, g0, cfg.seed, (uint64_t)iter,
+                                                    stream),
+                        "ptmh_accept_blocked"))
+                return false;
+            cnt.attempted_mutate += sub_decisions[m];
+        }
+        if (!HistoryAdd(nullptr)) return false;
+        iter++;
+        return true;
+    }
+
+    // SamplerPTChain::AdaptProposal's loop over blocks (SamplerPTChain.cpp:109-173)
+    bool AdaptBlocked()
+    {
+        if (!CheckNaN()) return false;
+        std::vector<float> h;
+        std::vector<int64_t> counts2;
+        if (!Download(h, hist, stream) || !Download(counts2, hcount, stream)) return false;
+        std::vector<int64_t> counts(C);
+        std::vector<uint8_t> active(C);
+        for (int64_t c = 0; c < C; c++) {
+            counts[c] = counts2[2 * c];
+            active[c] = temps_host[c] != 0.0;
+        }
+        const int64_t K = kmax;
+        std::vector<int32_t> nc(C * d, 1), dnc, dsel;
+        std::vector<double> w(C * d * K), lc(C * d * K), mu(C * K * d), L(C * K * d * d), dw, dlc, dmu, dL, dsc, dem;
+        int nthreads = cfg.host_threads > 0 ? cfg.host_threads
+                                            : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+        if (bcm3_adapt_proposals_blocked(kind, adjusted ? 1 : 0, (int)C, H, d, kmax, h.data(), counts.data(),
+                                         active.data(), (size_t)cfg.adapt_proposal_max_history_samples,
+                                         prior_mean.data(), prior_var.data(), cfg.seed, (uint64_t)cnt.adaptations_done,
+                                         g0, nthreads, bl_n.data(), bl_off.data(), bl_vars.data(), nc.data(), w.data(),
+                                         mu.data(), L.data(), lc.data(), nullptr) != 0)
+            return false;
+        // adapted chains get the fits and a fresh proposal's scales, per block
+        if (!Download(dnc, b_ncomp, stream) || !Download(dsel, b_selected, stream) || !Download(dw, b_weights, stream) ||
+            !Download(dlc, b_logc, stream) || !Download(dmu, b_mean, stream) || !Download(dL, b_chol, stream) ||
+            !Download(dsc, b_scale, stream) || !Download(dem, b_ema, stream))
+            return false;
+        const bool gmm = kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE;
+        for (int64_t c = 0; c < C; c++) {
+            if (!active[c]) continue;
+            std::copy(mu.begin() + c * K * d, mu.begin() + (c + 1) * K * d, dmu.begin() + c * K * d);
+            std::copy(L.begin() + c * K * d * d, L.begin() + (c + 1) * K * d * d, dL.begin() + c * K * d * d);
+            for (int b = 0; b < bl_n[c]; b++) {
+                const int s = BlockSize(c, b);
+                const int64_t cb = c * d + b;
+                const double tgt = (s == 1) ? 0.44 : (s == 2) ? 0.35 : (s == 3) ? 0.3 : 0.234;
+                dnc[cb] = nc[cb];
+                dsel[cb] = -1;
+                std::copy(w.begin() + cb * K, w.begin() + (cb + 1) * K, dw.begin() + cb * K);
+                std::copy(lc.begin() + cb * K, lc.begin() + (cb + 1) * K, dlc.begin() + cb * K);
+                std::fill(dsc.begin() + cb * K, dsc.begin() + (cb + 1) * K, gmm ? 2.38 / std::sqrt((double)s) : 1.0);
+                std::fill(dem.begin() + cb * K, dem.begin() + (cb + 1) * K, gmm ? tgt : 0.23);
+            }
+        }
+        if (!Upload(b_ncomp, dnc, stream) || !Upload(b_selected, dsel, stream) || !Upload(b_weights, dw, stream) ||
+            !Upload(b_logc, dlc, stream) || !Upload(b_mean, dmu, stream) || !Upload(b_chol, dL, stream) ||
+            !Upload(b_scale, dsc, stream) || !Upload(b_ema, dem, stream) ||
+            bcm3hip_memset_async(hcount.p, 0, hcount.n * sizeof(int64_t), stream) != 0)
+            return false;
+        if (!adapt_file.empty() && g0 + C == Ctot &&
+            !WriteAdaptationBlocks(cnt.adaptations_done + 1, C - 1, dnc, dw, dmu, dL, &h, counts))
+            return false;
+        cnt.adaptations_done++;
+        return bcm3hip_stream_synchronize(stream) == 0;
+    }
+
+    // adapt<index>/block<b + 1> of chain c's blocks (packed per-block state), then the file
+    bool WriteAdaptationBlocks(int64_t index, int64_t c, const std::vector<int32_t>& nc, const std::vector<double>& w,
+                               const std::vector<double>& mu, const std::vector<double>& L, const std::vector<float>* h,
+                               const std::vector<int64_t>& counts)
+    {
+        const int64_t K = kmax;
+        for (int b = 0; b < bl_n[c]; b++) {
+            const int o = BlockOffset(c, b), s = BlockSize(c, b);
+            const int32_t* v = BlockVars(c, b);
+            const int64_t cb = c * d + b;
+            AddAdaptationGroup(index, b + 1, std::vector<int32_t>(v, v + s), nc[cb], &w[(size_t)(cb * K)],
+                               &mu[(size_t)(c * K * d + K * o)], &L[(size_t)(c * K * d * d + K * o * d)], h, c,
+                               h ? counts[c] : 0);
+        }
+        if (!adapt_out.Write(adapt_file)) {
+            LOGERROR("Writing %s failed", adapt_file.c_str());
+            return false;
+        }
+        return true;
+    }
+
     bool HistoryAdd(const uint8_t* mask)
     {
         return Launch(bcm3hip_history_add((int)C, d, H, sub, temps.p, values.p, mask, hist.p, hcount.p, stream),
@@ -511,6 +715,7 @@ struct SamplerPTDevice::Impl {
     bool Mutate()
     {
         // DoMutateMove (SamplerPT.cpp:308-319): every chain's proposal in one likelihood launch
+        if (blocked) return MutateBlocked();
         if (adaptive) {
             if (!Launch(bcm3hip_ptmh_propose_adaptive((int)C, d, pkind.p, p0.p, p1.p, p2.p, temps.p, values.p, prop.p,
                                                       lprior_prop.p, log_mh.p, &P, g0, cfg.seed, (uint64_t)iter,
@@ -846,7 +1051,7 @@ struct SamplerPTDevice::Impl {
     bool SetupSpeculation()
     {
         spec_tail_on = getenv("BCM3_NO_SPEC_TAIL") == nullptr;
-        spec_on = cfg.speculate != 0 && adaptive && (cfg.world == 1 || transport) && cfg.swapping_scheme == 0 &&
+        spec_on = cfg.speculate != 0 && !blocked && adaptive && (cfg.world == 1 || transport) && cfg.swapping_scheme == 0 &&
                   cfg.exploration_steps == 1 && Ctot >= 2 && d <= 64 && C * (1 + BCM3HIP_SPEC_SLOTS) <= 4096 &&
                   ll->SupportsCountedBatch();
         if (!spec_on) return true;
@@ -948,6 +1153,7 @@ struct SamplerPTDevice::Impl {
     {
         // SamplerPTChain::AdaptProposal for every chain of the rank (T == 0 excepted), then the
         // history reset (SampleHistory::Reset)
+        if (blocked) return AdaptBlocked();
         if (!CheckNaN()) return false;
         std::vector<float> h;
         std::vector<int64_t> counts2;
@@ -1002,47 +1208,57 @@ struct SamplerPTDevice::Impl {
         return bcm3hip_stream_synchronize(stream) == 0;
     }
 
-    // adapt<index>/block1 of sampler_adaptation.nc for chain c's proposal; h == nullptr: no history
-    // group (adapt0, the proposal before any fit)
-    bool WriteAdaptation(int64_t index, int64_t c, const std::vector<int32_t>& nc, const std::vector<double>& w,
-                         const std::vector<double>& mu, const std::vector<double>& L, const std::vector<float>* h,
-                         const std::vector<int64_t>& counts)
+    // group adapt<index>/block<blockno> of sampler_adaptation.nc: a proposal over the variables
+    // `vars` (v of them) with K components -- weights w[K], means mu[K][v], factors L[K][v][v] --
+    // and, when h is given, the columns `vars` of chain c's history (rows as stored in the ring)
+    void AddAdaptationGroup(int64_t index, int blockno, const std::vector<int32_t>& vars, int K, const double* w,
+                            const double* mu, const double* L, const std::vector<float>* h, int64_t c, int64_t count)
     {
-        const std::string g = "adapt" + std::to_string(index) + "/block1";
-        std::vector<int32_t> ix(d);
-        for (int j = 0; j < d; j++) ix[j] = j;
-        adapt_out.AddVector(g, "variable_indices", ix);
+        const std::string g = "adapt" + std::to_string(index) + "/block" + std::to_string(blockno);
+        const int v = (int)vars.size();
+        adapt_out.AddVector(g, "variable_indices", vars);
         // covariance of component k = L_k L_k^T (the Cholesky factor the proposal state holds)
         auto cov = [&](int k) {
-            std::vector<double> S((size_t)d * d, 0.0);
-            const double* Lk = &L[(size_t)((c * kmax + k) * d * d)];
-            for (int i = 0; i < d; i++)
-                for (int j = 0; j < d; j++) {
+            std::vector<double> S((size_t)v * v, 0.0);
+            const double* Lk = L + (size_t)k * v * v;
+            for (int i = 0; i < v; i++)
+                for (int j = 0; j < v; j++) {
                     double s = 0.0;
-                    for (int m = 0; m <= std::min(i, j); m++) s += Lk[i * d + m] * Lk[j * d + m];
-                    S[(size_t)i * d + j] = s;
+                    for (int m = 0; m <= std::min(i, j); m++) s += Lk[i * v + m] * Lk[j * v + m];
+                    S[(size_t)i * v + j] = s;
                 }
             return S;
         };
         if (kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
-            const int K = nc[c];
-            adapt_out.AddVector(g, "gmm_weights", std::vector<double>(w.begin() + c * kmax, w.begin() + c * kmax + K));
+            adapt_out.AddVector(g, "gmm_weights", std::vector<double>(w, w + K));
             for (int k = 0; k < K; k++) {
-                const double* m = &mu[(size_t)((c * kmax + k) * d)];
-                adapt_out.AddVector(g, "cluster" + std::to_string(k) + "_mean", std::vector<double>(m, m + d));
-                adapt_out.AddMatrix(g, "cluster" + std::to_string(k) + "_covariance", d, d, cov(k));
+                const double* m = mu + (size_t)k * v;
+                adapt_out.AddVector(g, "cluster" + std::to_string(k) + "_mean", std::vector<double>(m, m + v));
+                adapt_out.AddMatrix(g, "cluster" + std::to_string(k) + "_covariance", v, v, cov(k));
             }
         } else {
-            adapt_out.AddMatrix(g, "covariance", d, d, cov(0));
+            adapt_out.AddMatrix(g, "covariance", v, v, cov(0));
         }
         if (h) {
             // the history this adaptation was fitted to (rows as stored in the device ring)
-            const int64_t rows = std::min<int64_t>(counts[c], H);
-            std::vector<double> hist((size_t)(rows * d));
+            const int64_t rows = std::min<int64_t>(count, H);
+            std::vector<double> hist((size_t)(rows * v));
             for (int64_t r = 0; r < rows; r++)
-                for (int j = 0; j < d; j++) hist[(size_t)(r * d + j)] = (*h)[(size_t)((c * H + r) * d + j)];
-            adapt_out.AddMatrix(g, "history", (size_t)rows, (size_t)d, hist);
+                for (int j = 0; j < v; j++) hist[(size_t)(r * v + j)] = (*h)[(size_t)((c * H + r) * d + vars[j])];
+            adapt_out.AddMatrix(g, "history", (size_t)rows, (size_t)v, hist);
         }
+    }
+
+    // adapt<index>/block1 of sampler_adaptation.nc for chain c's one-block proposal; h == nullptr: no
+    // history group (adapt0, the proposal before any fit)
+    bool WriteAdaptation(int64_t index, int64_t c, const std::vector<int32_t>& nc, const std::vector<double>& w,
+                         const std::vector<double>& mu, const std::vector<double>& L, const std::vector<float>* h,
+                         const std::vector<int64_t>& counts)
+    {
+        std::vector<int32_t> ix(d);
+        for (int j = 0; j < d; j++) ix[j] = j;
+        AddAdaptationGroup(index, 1, ix, nc[c], &w[(size_t)(c * kmax)], &mu[(size_t)(c * kmax * d)],
+                           &L[(size_t)(c * kmax * d * d)], h, c, h ? counts[c] : 0);
         if (!adapt_out.Write(adapt_file)) {
             LOGERROR("Writing %s failed", adapt_file.c_str());
             return false;
@@ -1184,6 +1400,14 @@ bool SamplerPTDevice::Initialize(std::shared_ptr<Likelihood> ll, const std::vect
     s.P.selected = s.selected.p;
     s.P.work = s.work.p;
     if (!s.InitProposal()) return false;
+    if (cfg.blocking != BCM3_PTMH_ONE_BLOCK) {
+        if (cfg.blocking != BCM3_PTMH_NO_BLOCKING && cfg.blocking != BCM3_PTMH_EXPLICIT_BLOCKS) {
+            LOGERROR("SamplerPTDevice: unknown blocking strategy %d", cfg.blocking);
+            return false;
+        }
+        s.blocked = true;
+        if (!s.SetupBlocks()) return false;
+    }
     for (int start = 0; start < 2; start++) {
         auto m = ExchangeParticipants(C, s.g0, s.Ctot, cfg.world, start, s.mask_all[start]);
         for (auto& v : m) {
@@ -1308,6 +1532,10 @@ bool SamplerPTDevice::SetAdaptationOutput(const std::string& filename)
     // an empty history: the prior-moment proposal InitProposal uploaded), no history group
     std::vector<int32_t> dnc;
     std::vector<double> dw, dmu, dL;
+    if (s.blocked)
+        return Download(dnc, s.b_ncomp, s.stream) && Download(dw, s.b_weights, s.stream) &&
+               Download(dmu, s.b_mean, s.stream) && Download(dL, s.b_chol, s.stream) &&
+               s.WriteAdaptationBlocks(0, s.C - 1, dnc, dw, dmu, dL, nullptr, std::vector<int64_t>());
     if (!Download(dnc, s.ncomp, s.stream) || !Download(dw, s.weights, s.stream) || !Download(dmu, s.mean, s.stream) ||
         !Download(dL, s.chol, s.stream))
         return false;
@@ -1330,8 +1558,41 @@ bool SamplerPTDevice::GetState(double* values, double* llh, double* lprior, doub
 
 bool SamplerPTDevice::GetProposalComponents(int32_t* nc)
 {
+    if (p_->blocked) {
+        std::vector<int32_t> all;
+        if (!nc || !Download(all, p_->b_ncomp, p_->stream)) return false;
+        for (int64_t c = 0; c < p_->C; c++) nc[c] = all[(size_t)(c * p_->d)];
+        return true;
+    }
     return nc && bcm3hip_memcpy_async(nc, p_->ncomp.p, p_->C * sizeof(int32_t), BCM3HIP_D2H, p_->stream) == 0 &&
            bcm3hip_stream_synchronize(p_->stream) == 0;
+}
+
+bool SamplerPTDevice::GetBlocks(int32_t* nblocks, int32_t* block_offset, int32_t* block_vars, int32_t* ncomp)
+{
+    Impl& s = *p_;
+    const int64_t C = s.C, d = s.d;
+    if (s.blocked) {
+        if (nblocks) std::copy(s.bl_n.begin(), s.bl_n.end(), nblocks);
+        if (block_offset) std::copy(s.bl_off.begin(), s.bl_off.end(), block_offset);
+        if (block_vars) std::copy(s.bl_vars.begin(), s.bl_vars.end(), block_vars);
+        std::vector<int32_t> all;
+        if (ncomp && !Download(all, s.b_ncomp, s.stream)) return false;
+        if (ncomp) std::copy(all.begin(), all.end(), ncomp);
+        return true;
+    }
+    std::vector<int32_t> nc(C, 1);
+    if (ncomp && s.adaptive && !GetProposalComponents(nc.data())) return false;
+    for (int64_t c = 0; c < C; c++) {
+        if (nblocks) nblocks[c] = 1;
+        for (int64_t i = 0; i <= d; i++)
+            if (block_offset) block_offset[c * (d + 1) + i] = (i == 0) ? 0 : (int32_t)d;
+        for (int64_t i = 0; i < d; i++) {
+            if (block_vars) block_vars[c * d + i] = (int32_t)i;
+            if (ncomp) ncomp[c * d + i] = (i == 0) ? nc[c] : 1;
+        }
+    }
+    return true;
 }
 
 PTMHCounters SamplerPTDevice::GetCounters()

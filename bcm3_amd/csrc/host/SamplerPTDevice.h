@@ -62,13 +62,20 @@ struct PTMHConfig {
     // one launch; bit-identical results. Used when the likelihood supports counted device batches
     // (the PopPK kernel), one rank, deterministic_even_odd, one exploration step, adaptive proposals.
     int speculate = 1;
+    // blocking strategy (SamplerPTChain.cpp:66-77): 0 one_block, 1 no_blocking (one variable per
+    // block), 2 explicit blocks (block_of_variable[d], ids 0..B-1 each used). With blocks a mutate
+    // move is one sub-move per block -- propose_blocked, one likelihood launch, accept_blocked --
+    // (SamplerPTChain.cpp:249-307), the proposals are adapted per block, and speculate is ignored
+    int blocking = 0;
+    std::vector<int32_t> block_of_variable;
 };
 
 struct PTMHCounters {
     int64_t attempted_mutate = 0, accepted_mutate = 0, attempted_exchange = 0, accepted_exchange = 0;
     int64_t samples_done = 0, adaptations_done = 0, iterations = 0, rounds = 0;
     // likelihood launches and the trajectories they evaluated, speculative candidates included
-    // (committed evaluations = attempted_mutate)
+    // (attempted_mutate = the accept decisions taken; with blocks the sub-moves' launches also
+    // evaluate the chains that have nothing to do in a sub-move)
     int64_t likelihood_launches = 0, evaluated_entries = 0;
 };
 
@@ -105,6 +112,9 @@ public:
     bool Synchronize();
     bool GetState(double* values, double* llh, double* lprior, double* lpp);
     bool GetProposalComponents(int32_t* ncomp);
+    // block tables of the rank's chains and the components of every block (any may be null):
+    // nblocks[C], block_offset[C][d + 1], block_vars[C][d], ncomp[C][d]
+    bool GetBlocks(int32_t* nblocks, int32_t* block_offset, int32_t* block_vars, int32_t* ncomp);
     PTMHCounters GetCounters();
     void* Stream() const { return stream_; }
     int64_t NumLocalChains() const { return C_; }

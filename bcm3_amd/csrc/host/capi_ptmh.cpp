@@ -88,6 +88,7 @@ int bcm3_run_config_from_file(const char* path, bcm3_run_config* out)
     r.ptmh.exchange_probability = p.exchange_probability;
     r.ptmh.initial_position_tries = p.initial_position_tries;
     r.ptmh.host_threads = p.host_threads;
+    r.ptmh.blocking = p.blocking;
     r.num_samples = rc.num_samples;
     r.output_proposal_adaptation = rc.output_proposal_adaptation ? 1 : 0;
     r.sampling_threads = rc.sampling_threads;
@@ -153,6 +154,14 @@ int bcm3_ptmh_create(bcm3_likelihood* ll, const char* prior_xml, const bcm3_ptmh
     cfg.nan_check_every = c->nan_check_every;
     cfg.host_threads = c->host_threads;
     cfg.speculate = c->speculate;
+    cfg.blocking = c->blocking;
+    if (c->blocking == BCM3_PTMH_EXPLICIT_BLOCKS) {
+        if (!c->block_of_variable) {
+            LOGERROR("bcm3_ptmh_create: explicit blocks need block_of_variable (one block id per variable)");
+            return -4;
+        }
+        cfg.block_of_variable.assign(c->block_of_variable, c->block_of_variable + prior.size());
+    }
     std::unique_ptr<bcm3::Transport> tr;
     if (c->world > 1) {
         if (c->transport == BCM3_PTMH_TRANSPORT_RCCL) {
@@ -212,6 +221,11 @@ int bcm3_ptmh_set_adaptation_output(bcm3_ptmh* h, const char* filename)
 }
 
 int bcm3_ptmh_get_components(bcm3_ptmh* h, int32_t* ncomp) { return (h && h->s.GetProposalComponents(ncomp)) ? 0 : -2; }
+
+int bcm3_ptmh_get_blocks(bcm3_ptmh* h, int32_t* nblocks, int32_t* block_offset, int32_t* block_vars, int32_t* ncomp)
+{
+    return (h && h->s.GetBlocks(nblocks, block_offset, block_vars, ncomp)) ? 0 : -2;
+}
 
 int bcm3_ptmh_get_counters(bcm3_ptmh* h, int64_t* out)
 {

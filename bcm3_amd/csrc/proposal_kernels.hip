@@ -13,6 +13,9 @@
 //   ptmh_accept_adaptive_kernel   TestSample with the MH ratio (SamplerPTChain.cpp:465-481), the
 //                                 state update and Proposal::NotifyAccepted (Proposal.cpp:210-220,
 //                                 ProposalGaussianMixture.cpp:91-103);
+//   ptmh_propose_blocked_kernel / ptmh_accept_blocked_kernel   the same moves per variable block
+//                                 (MutateMove's loop over blocks, SamplerPTChain.cpp:249-307) for
+//                                 blocking strategies other than one_block (bcm3hip_blocks);
 //   history_add_kernel            SampleHistory::AddSample (SampleHistory.cpp:32-45) after a mutate
 //                                 move (SamplerPTChain.cpp:309) or an exchange move (:374-379).
 //
@@ -728,6 +731,291 @@ __global__ void ptmh_accept_adaptive_kernel(int C, int d, const double* __restri
                accepted, nan_llh, P, chain0, seed, iter);
 }
 
+// ---- blocked moves (include/bcm3hip.h "blocked Metropolis-within-Gibbs moves") ----
+
+// the counter RNG's seed of sub-move m: the chain's own stream for m == 0
+__device__ __forceinline__ uint64_t submove_seed(uint64_t seed, int m)
+{
+    return seed + (uint64_t)m * 0x9E3779B97F4A7C15ull;
+}
+
+__device__ __forceinline__ int lane_bcast_i(int x, int j) { return __builtin_amdgcn_readlane(x, j); }
+
+// One wavefront per chain. Two index spaces: the full vector has lane i = variable i (copy, Dirichlet
+// residual, prior), the block's proposal has lane j = position j in the block (s = its size), with
+// the arithmetic of propose_wave_one in the block's dimensions -- its helpers are called with
+// d := s and the block's packed mean / factors -- so one block of all variables in order repeats
+// propose_wave_one operation for operation.
+__global__ void __launch_bounds__(64) ptmh_propose_blocked_kernel(
+    int C, int d, int m, const int32_t* __restrict__ kind, const double* __restrict__ p0, const double* __restrict__ p1,
+    const double* __restrict__ p2, const double* __restrict__ temps, const double* __restrict__ values,
+    double* __restrict__ prop, double* __restrict__ lprior_prop, double* __restrict__ log_mh, bcm3hip_proposal P,
+    bcm3hip_blocks B, int64_t chain0, uint64_t seed0, uint64_t iter)
+{
+    const int c = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    if (c >= C) return;
+    const int lane = threadIdx.x & 63;
+    const bool on = lane < d;
+    const int li = on ? lane : 0;
+    const uint64_t gc = (uint64_t)(chain0 + c);
+    const uint64_t seed = submove_seed(seed0, m);
+    const double cur = values[(int64_t)c * d + li];
+    double nxt = cur;
+    double lmh = 0.0;
+    const bool dir = prior::has_dirichlet(d, kind);
+    const double T = temps[c];
+    int nb = B.nblocks[c];
+    nb = (nb < 0) ? 0 : ((nb > d) ? d : nb);
+    const bool active = (T == 0.0) ? (m == 0) : (m < nb);
+    if (lane == 0) B.active[c] = active ? 1 : 0;
+    if (active && T == 0.0) {
+        nxt = prior::sample(kind[li], p0[li], p1[li], p2[li], seed, iter, gc, li);
+        if (dir) {
+            for (int f = 0; f < d; f++) {
+                if (kind[f] != BCM3HIP_PRIOR_DIRICHLET || (int)p1[f] != f) continue;
+                const int l = prior::dirichlet_last(d, kind, p1, f);
+                double sum = 0.0;
+                for (int j = f; j <= l; j++) sum += lane_bcast(nxt, j);
+                const double inv = 1.0 / sum;
+                if (lane >= f && lane <= l) nxt *= inv;
+            }
+        }
+    } else if (active) {
+        // the block: offset o, size s (clamped into the table, so a malformed table cannot index
+        // outside the chain's rows)
+        int o = B.block_offset[(int64_t)c * (d + 1) + m];
+        int s = B.block_offset[(int64_t)c * (d + 1) + m + 1] - o;
+        o = (o < 0) ? 0 : ((o > d - 1) ? d - 1 : o);
+        s = (s < 1) ? 1 : ((s > d - o) ? d - o : s);
+        const bool onb = lane < s;
+        const int lb = onb ? lane : 0;
+        int var = B.block_vars[(int64_t)c * d + o + lb];
+        var = (var < 0) ? 0 : ((var > d - 1) ? d - 1 : var);
+        const double curb = values[(int64_t)c * d + var];
+        const int Km = P.kmax;
+        const int64_t cb = (int64_t)c * d + m;
+        int K = (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) ? B.ncomp[cb] : 1;
+        K = (K < 1) ? 1 : ((K > Km) ? Km : K);
+        double* scale = B.scale + cb * Km;
+        const double* ema = B.ema + cb * Km;
+        const double* logc = B.logc + cb * Km;
+        const double* w = B.weights + cb * Km;
+        const double* mean = B.mean + (int64_t)c * Km * d + (int64_t)Km * o;
+        const double* chol = B.chol + (int64_t)c * Km * d * d + (int64_t)Km * o * d;
+        const double slr = P.scaling_learning_rate;
+        const double target = B.target[cb];
+        int sel;
+        double rf = 0.0;
+        int upd = -1;
+        double sc = 0.0;
+        if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
+            const int last = B.selected[cb];
+            if (last != -1) {
+                const double lrate = 1.0 + u01(rng_key(seed, iter, gc, rng::KEY_UPDATE)) * slr * K;
+                sc = scale[last];
+                const double e = ema[last];
+                if (e < target / (1.0 - slr)) {
+                    sc /= lrate;
+                    sc = (sc > 1e-4) ? sc : 1e-4;
+                } else if (e > (1 + slr) * target) {
+                    sc *= lrate;
+                    sc = (sc < 10.0) ? sc : 10.0;
+                }
+                if (lane == 0) scale[last] = sc;
+                upd = last;
+            }
+            rf = wave_responsibilities(K, s, curb, mean, chol, logc, w, lane);
+            const double u = u01(rng_key(seed, iter, gc, rng::KEY_SELECT));
+            double acc = 0.0;
+            sel = K - 1;
+            for (int k = 0; k < K; k++) {
+                acc += lane_bcast(rf, k);
+                if (u < acc) {
+                    sel = k;
+                    break;
+                }
+            }
+        } else {
+            const double lrate = 1.0 + u01(rng_key(seed, iter, gc, rng::KEY_UPDATE)) * slr;
+            sc = scale[0];
+            const double e = ema[0];
+            if (e < 0.952381 * target) {
+                sc /= lrate;
+                sc = (sc > 1e-4) ? sc : 1e-4;
+            } else if (e > 1.05 * target) {
+                sc *= lrate;
+                sc = (sc < 10.0) ? sc : 10.0;
+            }
+            if (lane == 0) scale[0] = sc;
+            upd = 0;
+            sel = 0;
+        }
+        double t_scale = 1.0;
+        if (P.t_dof > 0.0) {
+            const double wg = gamma_draw(0.5 * P.t_dof, 0.5 * P.t_dof, seed, iter, gc);
+            t_scale = 1.0 / sqrt(wg);
+        }
+        const double* Ls = chol + (int64_t)sel * s * s + (int64_t)lb * s;
+        const double z = normal01(seed, iter, gc, lb);
+        const double f = t_scale * ((sel == upd) ? sc : scale[sel]);
+        double x = 0.0;
+        for (int j = 0; j < s; j++) {
+            const double zj = lane_bcast(z, j);
+            const double a = x + Ls[j] * zj;
+            x = (j <= lane) ? a : x;
+        }
+        const double newb = reflect(x * f + curb, P.lower[var], P.upper[var]);
+        if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE && s <= 16) {
+            double r = 0.0, qv = 0.0;
+            for (int k = 0; k < K; k++) {
+                const double sk = (k == upd) ? sc : scale[k];
+                const double ta0 = onb ? newb - mean[k * s + lane] : 0.0;
+                const double tb0 = onb ? (newb - curb) / sk : 0.0;
+                double ta, tb;
+                wave_lower_solve2_reg<16>(s, chol + (int64_t)k * s * s + (int64_t)lb * s, ta0, tb0, lane, ta, tb);
+                const double rk = (logc[k] - 0.5 * wave_seq_sum(s, onb ? ta * ta : 0.0)) + log(w[k]);
+                r = (lane == k) ? rk : r;
+                const double q = 0.5 * wave_seq_sum(s, onb ? tb * tb : 0.0);
+                qv = (lane == k) ? q : qv;
+            }
+            double lsum;
+            const double rr = wave_normalize_resp(K, r, lsum);
+            double fwd = -INFINITY, rev = -INFINITY;
+            for (int k = 0; k < K; k++) {
+                const double sk = (k == upd) ? sc : scale[k];
+                const double base = -log(sk * sk) + logc[k];
+                const double q = lane_bcast(qv, k);
+                fwd = logsum2(fwd, (base - q) + log(lane_bcast(rf, k)));
+                rev = logsum2(rev, (base - q) + log(lane_bcast(rr, k)));
+            }
+            lmh = rev - fwd;
+        } else if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
+            const double rr = wave_responsibilities(K, s, newb, mean, chol, logc, w, lane);
+            double fwd = -INFINITY, rev = -INFINITY;
+            for (int k = 0; k < K; k++) {
+                const double sk = (k == upd) ? sc : scale[k];
+                const double t0 = onb ? (newb - curb) / sk : 0.0;
+                const double t = wave_lower_solve(s, chol + (int64_t)k * s * s + (int64_t)lb * s, t0, lane);
+                const double base = -log(sk * sk) + logc[k];
+                const double q = 0.5 * wave_seq_sum(s, onb ? t * t : 0.0);
+                fwd = logsum2(fwd, (base - q) + log(lane_bcast(rf, k)));
+                rev = logsum2(rev, (base - q) + log(lane_bcast(rr, k)));
+            }
+            lmh = rev - fwd;
+        }
+        // the block's new coordinates into the full vector (lane = variable), the rest unchanged
+        for (int j = 0; j < s; j++) {
+            const int vj = lane_bcast_i(var, j);
+            const double xj = lane_bcast(newb, j);
+            nxt = (lane == vj) ? xj : nxt;
+        }
+        if (dir) {
+            // Dirichlet residual after the MH ratio of the unmodified proposal (SamplerPTChain.cpp:270-278);
+            // the residual may lie outside the block
+            for (int f = 0; f < d; f++) {
+                if (kind[f] != BCM3HIP_PRIOR_DIRICHLET || (int)p1[f] != f) continue;
+                const int l = prior::dirichlet_last(d, kind, p1, f);
+                double sum = 0.0;
+                for (int j = f; j < l; j++) sum += lane_bcast(nxt, j);
+                if (lane == l) nxt = 1.0 - sum;
+            }
+        }
+        if (lane == 0) B.selected[cb] = sel;
+    }
+    if (on) prop[(int64_t)c * d + lane] = nxt;
+    double lp;
+    if (!dir) {
+        lp = wave_seq_sum(d, on ? prior::log_pdf(kind[li], p0[li], p1[li], p2[li], nxt) : 0.0);
+    } else {
+        const double ul = (on && kind[li] != BCM3HIP_PRIOR_DIRICHLET) ? prior::log_pdf(kind[li], p0[li], p1[li], p2[li], nxt)
+                                                                        : 0.0;
+        lp = 0.0;
+        for (int f = 0; f < d; f++)
+            if (kind[f] == BCM3HIP_PRIOR_DIRICHLET && (int)p1[f] == f)
+                lp += prior::dirichlet_log_pdf(f, prior::dirichlet_last(d, kind, p1, f), p0, p2[f],
+                                               [&](int j) { return lane_bcast(nxt, j); });
+        for (int i = 0; i < d; i++)
+            if (kind[i] != BCM3HIP_PRIOR_DIRICHLET) lp += lane_bcast(ul, i);
+    }
+    if (lane == 0) {
+        lprior_prop[c] = lp;
+        log_mh[c] = lmh;
+    }
+}
+
+// accept_one for a blocked move: the component that proposed and its acceptance EMA are the block's
+// (sel_p, ema_row)
+__device__ __forceinline__ bool accept_block_one(int c, int d, const double* __restrict__ temps, const double* __restrict__ prop,
+                           const double* __restrict__ lprior_prop, const double* __restrict__ llh_prop,
+                           const double* __restrict__ log_mh, double learning_rate, double* __restrict__ values,
+                           double* __restrict__ lprior, double* __restrict__ llh, double* __restrict__ lpp,
+                           uint8_t* __restrict__ acc_out, unsigned long long* __restrict__ accepted,
+                           int32_t* __restrict__ nan_llh, const int32_t* sel_p, double* ema_row, double ema_period,
+                           int64_t chain0, uint64_t seed, uint64_t iter)
+{
+    const double T = temps[c];
+    const double nl = llh_prop[c] * learning_rate;  // Sampler::EvaluateLikelihood
+    const double nq = lprior_prop[c];
+    bool acc;
+    double npp;
+    if (isnan(nl)) {
+        // Sampler::EvaluateLikelihood (Sampler.cpp:172-178): a NaN log-likelihood is fatal; the
+        // chain keeps its state (no EMA update) and the host raises at its next check of the flag
+        if (nan_llh) *nan_llh = 1;
+        acc = false;
+        npp = 0.0;
+    } else if (T == 0.0) {
+        acc = true;
+        npp = (nl == -INFINITY) ? nq : nq + T * nl;
+    } else {
+        npp = nq + T * nl;
+        acc = false;
+        if (npp > -INFINITY) {
+            double tp = npp - lpp[c];
+            tp = exp(tp + log_mh[c]);
+            tp = (tp < 1.0) ? tp : 1.0;  // std::min((Real)1.0, tp): NaN -> 1
+            acc = u01(rng_key(seed, iter, (uint64_t)(chain0 + c), rng::KEY_ACCEPT)) < tp;
+        }
+        // NotifyAccepted (EMA of the acceptance of the component that proposed)
+        const int sel = *sel_p;
+        double* ema = ema_row + sel;
+        const double alpha = 2.0 / (ema_period + 1);
+        *ema += ((acc ? 1.0 : 0.0) - *ema) * alpha;
+    }
+    if (acc) {
+        copy_row(values + (int64_t)c * d, prop + (int64_t)c * d, d);
+        lprior[c] = nq;
+        llh[c] = nl;
+        lpp[c] = npp;
+    }
+    if (acc_out) acc_out[c] = acc ? 1 : 0;
+    if (accepted && acc) atomicAdd(accepted, 1ull);
+    return acc;
+}
+
+__global__ void ptmh_accept_blocked_kernel(int C, int d, int m, const double* __restrict__ temps,
+                                           const double* __restrict__ prop, const double* __restrict__ lprior_prop,
+                                           const double* __restrict__ llh_prop, const double* __restrict__ log_mh,
+                                           double learning_rate, double* __restrict__ values,
+                                           double* __restrict__ lprior, double* __restrict__ llh,
+                                           double* __restrict__ lpp, uint8_t* __restrict__ acc_out,
+                                           unsigned long long* __restrict__ accepted, int32_t* __restrict__ nan_llh,
+                                           bcm3hip_proposal P, bcm3hip_blocks B, int64_t chain0, uint64_t seed,
+                                           uint64_t iter)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    if (!B.active[c]) {
+        if (acc_out) acc_out[c] = 0;
+        return;
+    }
+    // (an active T == 0 chain has m == 0 and reads neither the selection nor the EMAs)
+    const int64_t cb = (int64_t)c * d + m;
+    accept_block_one(c, d, temps, prop, lprior_prop, llh_prop, log_mh, learning_rate, values, lprior, llh, lpp, acc_out,
+                     accepted, nan_llh, B.selected + cb, B.ema + cb * P.kmax, P.scaling_ema_period, chain0,
+                submove_seed(seed, m), iter);
+}
+
 // SampleHistory::AddSample for the chains with T != 0 (and mask[c] != 0 when a mask is given):
 // every `subsampling`-th call stores the values as float in slot n % H of the chain's ring
 __device__ __forceinline__ void history_one(int c, int d, int H, int subsampling, const double* __restrict__ temps,
@@ -1351,6 +1639,53 @@ int bcm3hip_ptmh_accept_adaptive(int C, int d, const double* temps, const double
     hipLaunchKernelGGL(ptmh_accept_adaptive_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, C, d,
                        temps, prop, lprior_prop, llh_prop, log_mh, learning_rate, values, lprior, llh, lpp, accept_out,
                        (unsigned long long*)accepted, nan_llh, *proposal, chain0, seed, iter);
+    return hipGetLastError() == hipSuccess ? 0 : BCM3HIP_ERR_HIP;
+}
+
+// blocked moves read kind, kmax, t_dof, the scaling constants and the bounds of the proposal struct
+static bool blocked_ok(const bcm3hip_proposal* P, const bcm3hip_blocks* B, int C, int d, int submove)
+{
+    if (!P || !B || d > 64 || submove < 0 || submove >= d) return false;
+    if (P->kind != BCM3HIP_PROPOSAL_GLOBAL_COVARIANCE && P->kind != BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) return false;
+    if (P->kmax < 1 || P->kmax > BCM3HIP_PROPOSAL_KMAX) return false;
+    if (C > 0 && (!P->lower || !P->upper || !B->nblocks || !B->block_offset || !B->block_vars || !B->target ||
+                  !B->ncomp || !B->selected || !B->weights || !B->logc || !B->scale || !B->ema || !B->mean ||
+                  !B->chol || !B->active))
+        return false;
+    return true;
+}
+
+int bcm3hip_ptmh_propose_blocked(int C, int d, int submove, const int32_t* prior_kind, const double* prior_p0,
+                                 const double* prior_p1, const double* prior_p2, const double* temps,
+                                 const double* values, double* prop, double* lprior_prop, double* log_mh,
+                                 const bcm3hip_proposal* proposal, const bcm3hip_blocks* blocks, int64_t chain0,
+                                 uint64_t seed, uint64_t iter, void* stream)
+{
+    if (C < 0 || d <= 0 || !blocked_ok(proposal, blocks, C, d, submove) ||
+        (C > 0 && (!prior_kind || !prior_p0 || !prior_p1 || !prior_p2 || !temps || !values || !prop ||
+                   !lprior_prop || !log_mh)))
+        return BCM3HIP_ERR_ARG;
+    if (C == 0) return 0;
+    hipLaunchKernelGGL(ptmh_propose_blocked_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, C, d, submove,
+                       prior_kind, prior_p0, prior_p1, prior_p2, temps, values, prop, lprior_prop, log_mh, *proposal,
+                       *blocks, chain0, seed, iter);
+    return hipGetLastError() == hipSuccess ? 0 : BCM3HIP_ERR_HIP;
+}
+
+int bcm3hip_ptmh_accept_blocked(int C, int d, int submove, const double* temps, const double* prop,
+                                const double* lprior_prop, const double* llh_prop, const double* log_mh,
+                                double learning_rate, double* values, double* lprior, double* llh, double* lpp,
+                                uint8_t* accept_out, uint64_t* accepted, int32_t* nan_llh,
+                                const bcm3hip_proposal* proposal, const bcm3hip_blocks* blocks, int64_t chain0,
+                                uint64_t seed, uint64_t iter, void* stream)
+{
+    if (C < 0 || d <= 0 || !blocked_ok(proposal, blocks, C, d, submove) ||
+        (C > 0 && (!temps || !prop || !lprior_prop || !llh_prop || !log_mh || !values || !lprior || !llh || !lpp)))
+        return BCM3HIP_ERR_ARG;
+    if (C == 0) return 0;
+    hipLaunchKernelGGL(ptmh_accept_blocked_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, C, d,
+                       submove, temps, prop, lprior_prop, llh_prop, log_mh, learning_rate, values, lprior, llh, lpp,
+                       accept_out, (unsigned long long*)accepted, nan_llh, *proposal, *blocks, chain0, seed, iter);
     return hipGetLastError() == hipSuccess ? 0 : BCM3HIP_ERR_HIP;
 }
 

@@ -241,6 +241,148 @@ class DeviceProposal:
         self._reset_scales(active, initial=False)
 
 
+class BlockedProposal:
+    """Per-(chain, block) proposal state of C chains for a partition of the d variables into
+    blocks (bcm3hip_blocks, include/bcm3hip.h): SamplerPTChain's one Proposal object per variable
+    block (src/sampler/SamplerPTChain.cpp:66-77, 109-173). nblocks / block_offset / block_vars: one
+    chain's table (bcm3_amd.ptmh.build_blocks), given to every chain; the device layout stays per
+    chain. base: the chain-level DeviceProposal (kind, kmax, bounds, prior moments). The state starts
+    as every block's prior-moment proposal, as the reference's adaptation on the empty history in
+    SamplerPTChain::Initialize leaves it."""
+
+    def __init__(self, base: DeviceProposal, nblocks: int, block_offset, block_vars):
+        self.base = base
+        C, d, K = base.C, base.d, base.kmax
+        dev = base.chol.device
+        self.C, self.d, self.kmax = C, d, K
+        self.off = np.ascontiguousarray(block_offset, dtype=np.int32)
+        self.vars = np.ascontiguousarray(block_vars, dtype=np.int32)
+        self.nb = int(nblocks)
+        self.h_nblocks = np.full(C, self.nb, dtype=np.int32)
+        self.h_offset = np.ascontiguousarray(np.tile(self.off, (C, 1)))
+        self.h_vars = np.ascontiguousarray(np.tile(self.vars, (C, 1)))
+        self.gmm = base.kind == "gaussian_mixture"
+        pm = base.prior_mean.to("cpu").numpy()
+        pv = base.prior_var.to("cpu").numpy()
+        target = np.full((C, d), 0.234)
+        ncomp = np.ones((C, d), dtype=np.int32)
+        weights = np.zeros((C, d, K))
+        logc = np.zeros((C, d, K))
+        scale = np.ones((C, d, K))
+        ema = np.full((C, d, K), 0.23)
+        mean = np.zeros((C, K * d))
+        chol = np.zeros((C, K * d * d))
+        for b in range(self.nb):
+            o, s = int(self.off[b]), int(self.off[b + 1] - self.off[b])
+            v = self.vars[o:o + s]
+            target[:, b] = target_acceptance_rate(s)
+            sd = np.sqrt(pv[v])
+            det = 0.0
+            for x in sd.tolist():
+                det += math.log(x)
+            weights[:, b, 0] = 1.0
+            mean[:, K * o:K * o + s] = pm[v]
+            for k in range(K):
+                L = np.diag(sd) if k == 0 else np.eye(s)
+                chol[:, K * o * d + k * s * s:K * o * d + (k + 1) * s * s] = L.reshape(-1)
+                logc[:, b, k] = (-det if k == 0 else -0.0) - 0.5 * s * math.log(2.0 * math.pi)
+            if self.gmm:
+                scale[:, b, :] = 2.38 / math.sqrt(s)
+                ema[:, b, :] = target_acceptance_rate(s)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        self.nblocks, self.block_offset, self.block_vars = t(self.h_nblocks), t(self.h_offset), t(self.h_vars)
+        self.target, self.ncomp = t(target), t(ncomp)
+        self.selected = torch.full((C, d), -1, dtype=torch.int32, device=dev)
+        self.weights, self.logc, self.scale, self.ema = t(weights), t(logc), t(scale), t(ema)
+        self.mean, self.chol = t(mean), t(chol)
+        self.active = torch.zeros(C, dtype=torch.uint8, device=dev)
+        self.struct = _hip.Blocks(
+            nblocks=self.nblocks.data_ptr(), block_offset=self.block_offset.data_ptr(),
+            block_vars=self.block_vars.data_ptr(), target=self.target.data_ptr(), ncomp=self.ncomp.data_ptr(),
+            selected=self.selected.data_ptr(), weights=self.weights.data_ptr(), logc=self.logc.data_ptr(),
+            scale=self.scale.data_ptr(), ema=self.ema.data_ptr(), mean=self.mean.data_ptr(),
+            chol=self.chol.data_ptr(), active=self.active.data_ptr())
+
+    def block(self, b: int):
+        """(offset, size, variables) of block b"""
+        o, s = int(self.off[b]), int(self.off[b + 1] - self.off[b])
+        return o, s, self.vars[o:o + s]
+
+    def set_mixture(self, chain: int, b: int, weights, means, covariances):
+        """Load a mixture over block b's variables for one chain (DeviceProposal.set_mixture)."""
+        o, s, _ = self.block(b)
+        K, d, Km = len(weights), self.d, self.kmax
+        if not (self.gmm and 1 <= K <= Km):
+            raise ValueError(f"{K} components need a gaussian_mixture proposal with kmax >= {K}")
+        L = np.tile(np.eye(s), (Km, 1, 1))
+        L[:K] = np.linalg.cholesky(np.asarray(covariances, dtype=np.float64).reshape(K, s, s))
+        mu = np.zeros((Km, s))
+        mu[:K] = np.asarray(means, dtype=np.float64).reshape(K, s)
+        w = np.zeros(Km)
+        w[:K] = weights
+        dev = self.chol.device
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        self.ncomp[chain, b] = K
+        self.weights[chain, b] = t(w)
+        self.mean[chain, Km * o:Km * (o + s)] = t(mu.reshape(-1))
+        self.chol[chain, Km * o * d:Km * o * d + Km * s * s] = t(L.reshape(-1))
+        self.logc[chain, b] = log_normaliser(t(L))
+        self.scale[chain, b] = 2.38 / math.sqrt(s)
+        self.ema[chain, b] = target_acceptance_rate(s)
+        self.selected[chain, b] = -1
+
+    def adapt(self, history: torch.Tensor, counters: torch.Tensor, seed: int = 0, adaptation: int = 0,
+              chain0: int = 0, max_history_samples: int = 2000, adjusted_aic: bool = False,
+              nthreads: Optional[int] = None):
+        """DeviceProposal.adapt per block (bcm3_adapt_proposals_blocked): every block of every chain
+        at T != 0 gets the fit on its own history columns and a fresh proposal's scales."""
+        from .likelihood import lib as host_lib
+        C, H, d = history.shape
+        K = self.kmax
+        hist = np.ascontiguousarray(history.detach().to("cpu").numpy(), dtype=np.float32)
+        counts = np.ascontiguousarray(counters[:, 0].detach().to("cpu").numpy(), dtype=np.int64)
+        active = np.ascontiguousarray((self.base.temps != 0.0).to("cpu").numpy(), dtype=np.uint8)
+        pm = np.ascontiguousarray(self.base.prior_mean.to("cpu").numpy(), dtype=np.float64)
+        pv = np.ascontiguousarray(self.base.prior_var.to("cpu").numpy(), dtype=np.float64)
+        ncomp = np.ones((C, d), dtype=np.int32)
+        fitted = np.zeros((C, d), dtype=np.int32)
+        w, lc = np.zeros((C, d, K)), np.zeros((C, d, K))
+        mu, L = np.zeros((C, K * d)), np.zeros((C, K * d * d))
+        if nthreads is None:
+            nthreads = max(1, min(16, len(os.sched_getaffinity(0))))
+        Lb = host_lib()
+        rc = Lb.bcm3_adapt_proposals_blocked(
+            1 if self.gmm else 0, int(adjusted_aic), C, H, d, K, hist.ctypes.data, counts.ctypes.data,
+            active.ctypes.data, int(max_history_samples), pm.ctypes.data, pv.ctypes.data, int(seed) & ((1 << 64) - 1),
+            int(adaptation), int(chain0), int(nthreads), self.h_nblocks.ctypes.data, self.h_offset.ctypes.data,
+            self.h_vars.ctypes.data, ncomp.ctypes.data, w.ctypes.data, mu.ctypes.data, L.ctypes.data, lc.ctypes.data,
+            fitted.ctypes.data)
+        if rc != 0:
+            msg = Lb.bcm3_last_error()
+            raise RuntimeError(f"proposal adaptation failed: {msg.decode() if msg else rc}")
+        dev = self.chol.device
+        act = torch.from_numpy(active.astype(bool)).to(dev)
+        m1, m2 = act.view(-1, 1), act.view(-1, 1, 1)
+        used = torch.arange(d, device=dev).view(1, -1) < self.nblocks.view(-1, 1)  # blocks in use
+        mb = m1 & used
+        self.ncomp.copy_(torch.where(mb, torch.from_numpy(ncomp).to(dev), self.ncomp))
+        self.selected.copy_(torch.where(mb, torch.full_like(self.selected, -1), self.selected))
+        self.weights.copy_(torch.where(mb.unsqueeze(-1), torch.from_numpy(w).to(dev), self.weights))
+        self.logc.copy_(torch.where(mb.unsqueeze(-1), torch.from_numpy(lc).to(dev), self.logc))
+        self.mean.copy_(torch.where(m1, torch.from_numpy(mu).to(dev), self.mean))
+        self.chol.copy_(torch.where(m1, torch.from_numpy(L).to(dev), self.chol))
+        s0 = np.ones((C, d, K))
+        e0 = np.full((C, d, K), 0.23)
+        if self.gmm:
+            for b in range(self.nb):
+                s = int(self.off[b + 1] - self.off[b])
+                s0[:, b, :] = 2.38 / math.sqrt(s)
+                e0[:, b, :] = target_acceptance_rate(s)
+        self.scale.copy_(torch.where(mb.unsqueeze(-1), torch.from_numpy(s0).to(dev), self.scale))
+        self.ema.copy_(torch.where(mb.unsqueeze(-1), torch.from_numpy(e0).to(dev), self.ema))
+        self.last_fitted = fitted
+
+
 class SampleHistory:
     """Per-chain float ring buffer in HBM (SampleHistory.cpp:14-45)."""
 

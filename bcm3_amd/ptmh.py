@@ -19,6 +19,7 @@ from .likelihood import Likelihood, lib as host_lib
 
 PROPOSALS = {"global_covariance": 0, "gaussian_mixture": 1, "gaussian_mixture_adjustedAIC": 2, "random_walk": 3}
 SCHEMES = {"deterministic_even_odd": 0, "stochastic_even_odd": 1, "stochastic_random": 2}
+BLOCKINGS = {"one_block": 0, "no_blocking": 1, "explicit": 2}
 TRANSPORT_NONE, TRANSPORT_RCCL, TRANSPORT_LOCAL, TRANSPORT_SOCKET = 0, 1, 2, 3
 COUNTERS = ("attempted_mutate", "accepted_mutate", "attempted_exchange", "accepted_exchange", "samples_done",
             "adaptations_done", "iterations", "rounds", "likelihood_launches", "evaluated_entries")
@@ -37,6 +38,7 @@ class PTMHConfig(C.Structure):
         ("speculate", C.c_int32),
         ("transport", C.c_int32), ("nccl_id", C.c_uint8 * 128), ("group", C.c_void_p),
         ("socket_dir", C.c_char * 256),
+        ("blocking", C.c_int32), ("block_of_variable", C.POINTER(C.c_int32)),
     ]
 
 
@@ -76,6 +78,8 @@ def _lib():
         L.bcm3_ptmh_num_chains.argtypes = [vp]
         L.bcm3_ptmh_get_state.argtypes = [vp, vp, vp, vp, vp]
         L.bcm3_ptmh_get_components.argtypes = [vp, vp]
+        L.bcm3_ptmh_get_blocks.argtypes = [vp, vp, vp, vp, vp]
+        L.bcm3_build_blocks.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp]
         L.bcm3_ptmh_get_counters.argtypes = [vp, vp]
         L.bcm3_ptmh_stream.argtypes = [vp]
         L.bcm3_ptmh_stream.restype = vp
@@ -106,7 +110,8 @@ def load_config(path: str) -> dict:
     would reject."""
     rc = RunConfig()
     _check(_lib().bcm3_run_config_from_file(path.encode(), C.byref(rc)), "bcm3_run_config_from_file")
-    ptmh = {k: getattr(rc.ptmh, k) for k, _ in PTMHConfig._fields_ if k not in ("nccl_id", "group", "socket_dir")}
+    ptmh = {k: getattr(rc.ptmh, k) for k, _ in PTMHConfig._fields_
+            if k not in ("nccl_id", "group", "socket_dir", "block_of_variable")}
     out = {"ptmh": ptmh}
     for k, _ in RunConfig._fields_:
         if k in ("ptmh", "pad_"):
@@ -114,6 +119,24 @@ def load_config(path: str) -> dict:
         v = getattr(rc, k)
         out[k] = v.decode() if isinstance(v, bytes) else v
     return out
+
+
+def build_blocks(blocking: str, d: int, blocks=None):
+    """The block table of a blocking strategy (bcm3_build_blocks): blocking "one_block" |
+    "no_blocking" | "explicit" with blocks = the block id of each of the d variables (0..B-1, each
+    used). Returns (nblocks, block_offset[d + 1], block_vars[d]); raises RuntimeError with the
+    library's message for an invalid partition."""
+    off = np.zeros(d + 1, dtype=np.int32)
+    var = np.zeros(d, dtype=np.int32)
+    nb = C.c_int32()
+    ids = None
+    if blocks is not None:
+        ids = np.ascontiguousarray(blocks, dtype=np.int32)
+        if ids.shape != (d,):
+            raise RuntimeError(f"blocks has {ids.size} entries for {d} variables")
+    _check(_lib().bcm3_build_blocks(BLOCKINGS[blocking], d, None if ids is None else ids.ctypes.data, C.addressof(nb),
+                                    off.ctypes.data, var.ctypes.data), "bcm3_build_blocks")
+    return int(nb.value), off, var
 
 
 def nccl_unique_id() -> bytes:
@@ -142,7 +165,11 @@ class PTMHNative:
     def __init__(self, likelihood: Likelihood, prior_xml: str, num_chains: int, rank: int = 0, world: int = 1,
                  seed: int = 0, proposal: str = "gaussian_mixture", swapping_scheme: str = "deterministic_even_odd",
                  stream: Optional[int] = None, transport: int = TRANSPORT_NONE, nccl_id: Optional[bytes] = None,
-                 group: Optional[LocalGroup] = None, socket_dir: Optional[str] = None, **options):
+                 group: Optional[LocalGroup] = None, socket_dir: Optional[str] = None, blocking: str = "one_block",
+                 blocks=None, **options):
+        """blocking: "one_block" (default), "no_blocking" (one variable per block) or "explicit" with
+        blocks = the block id of every variable (0..B-1, each used; giving blocks alone implies
+        "explicit"). With blocks a mutate move is one sub-move per block and `speculate` is ignored."""
         _hip.lib()
         L = _lib()
         cfg = PTMHConfig()
@@ -163,6 +190,14 @@ class PTMHNative:
             if k not in dict(PTMHConfig._fields_):
                 raise ValueError(f"unknown sampler option {k}")
             setattr(cfg, k, v)
+        if blocks is not None and blocking == "one_block":
+            blocking = "explicit"
+        cfg.blocking = BLOCKINGS[blocking]
+        if blocking == "explicit":
+            if blocks is None or len(blocks) != likelihood.d:
+                raise RuntimeError(f"blocks needs one block id for each of the {likelihood.d} variables")
+            self._blocks = (C.c_int32 * likelihood.d)(*[int(b) for b in blocks])  # read by bcm3_ptmh_create
+            cfg.block_of_variable = self._blocks
         self.ll = likelihood  # keeps the likelihood alive
         h = C.c_void_p()
         _check(L.bcm3_ptmh_create(likelihood.h, prior_xml.encode(), C.byref(cfg), stream, C.byref(h)),
@@ -220,6 +255,17 @@ class PTMHNative:
         nc = np.empty(self.C, dtype=np.int32)
         _check(_lib().bcm3_ptmh_get_components(self.h, nc.ctypes.data), "bcm3_ptmh_get_components")
         return nc
+
+    def blocks(self):
+        """The rank's block tables and every block's mixture components (bcm3_ptmh_get_blocks):
+        dict(nblocks [C], block_offset [C][d + 1], block_vars [C][d], ncomp [C][d])."""
+        nb = np.empty(self.C, dtype=np.int32)
+        off = np.empty((self.C, self.d + 1), dtype=np.int32)
+        var = np.empty((self.C, self.d), dtype=np.int32)
+        nc = np.empty((self.C, self.d), dtype=np.int32)
+        _check(_lib().bcm3_ptmh_get_blocks(self.h, nb.ctypes.data, off.ctypes.data, var.ctypes.data, nc.ctypes.data),
+               "bcm3_ptmh_get_blocks")
+        return dict(nblocks=nb, block_offset=off, block_vars=var, ncomp=nc)
 
     def counters(self):
         out = np.empty(len(COUNTERS), dtype=np.int64)

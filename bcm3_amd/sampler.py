@@ -227,7 +227,11 @@ class PTMHDevice:
                  adapt_proposal_samples: int = 2000, adapt_proposal_times: int = 2, max_history_size: int = 2000,
                  use_every_nth: int = 1, swapping_scheme: str = "deterministic_even_odd",
                  exchange_probability: float = 0.5, initial_position_tries: int = 100,
-                 adapt_proposal_max_history_samples: int = 2000):
+                 adapt_proposal_max_history_samples: int = 2000, blocking: str = "one_block", blocks=None):
+        """blocking / blocks: the variable blocks of the mutate move as bcm3_amd.ptmh.PTMHNative takes
+        them ("one_block", "no_blocking", or "explicit" with one block id per variable): one sub-move
+        per block -- propose_blocked, the likelihood launch, accept_blocked -- then one history add
+        (SamplerPTChain.cpp:249-309), proposals adapted per block."""
         from . import _hip
         self._hip = _hip
         _hip.lib()  # fails loudly without the HIP library
@@ -291,6 +295,16 @@ class PTMHDevice:
             self.history = SampleHistory(C, d, H, sub, dev)
             self.log_mh = torch.zeros(C, dtype=torch.float64, device=dev)
             self._masks = {start: self._exchange_masks(start) for start in (0, 1)}
+        if blocks is not None and blocking == "one_block":
+            blocking = "explicit"
+        self.blocked = None
+        if blocking != "one_block":
+            if not self.adaptive or d > 64:
+                raise ValueError("variable blocks need an adaptive proposal and at most 64 variables")
+            from .ptmh import build_blocks
+            from .proposal import BlockedProposal
+            self.blocked = BlockedProposal(self.proposal, *build_blocks(blocking, d, blocks))
+            self._cold = int((self.T == 0.0).sum().item())  # T == 0 chains: prior draws in sub-move 0 only
         self._initial_positions(initial_position_tries)
 
     def _initial_positions(self, tries: int):
@@ -365,6 +379,25 @@ class PTMHDevice:
     def mutate(self):
         """DoMutateMove (SamplerPT.cpp:308-319): all chains' proposals in one likelihood launch."""
         h, C, d, st = self._hip, self.C, self.d, self._stream()
+        if self.blocked is not None:
+            P, B = self.proposal.struct, self.blocked
+            cold = self._cold
+            for m in range(B.nb):
+                h.ptmh_propose_blocked(C, d, m, self.kind.data_ptr(), self.p0.data_ptr(), self.p1.data_ptr(),
+                                       self.p2.data_ptr(), self.T.data_ptr(), self.values.data_ptr(),
+                                       self.prop.data_ptr(), self.lprior_prop.data_ptr(), self.log_mh.data_ptr(), P,
+                                       B.struct, self.g0, self.seed, self.iter, st)
+                self._eval(self.prop, self.llh_prop)
+                h.ptmh_accept_blocked(C, d, m, self.T.data_ptr(), self.prop.data_ptr(), self.lprior_prop.data_ptr(),
+                                      self.llh_prop.data_ptr(), self.log_mh.data_ptr(), self.lr,
+                                      self.values.data_ptr(), self.lprior.data_ptr(), self.llh.data_ptr(),
+                                      self.lpp.data_ptr(), None, self.accepted_mutate.data_ptr(), P, B.struct, self.g0,
+                                      self.seed, self.iter, st, nan_llh=self.nan_llh.data_ptr())
+                # accept decisions taken: every T != 0 chain, the T == 0 chains in sub-move 0 only
+                self.attempted_mutate += C - cold + (cold if m == 0 else 0)
+            self.history.add(self.T, self.values, None, st)  # SamplerPTChain.cpp:309
+            self.iter += 1
+            return
         if self.adaptive:
             P = self.proposal.struct
             h.ptmh_propose_adaptive(C, d, self.kind.data_ptr(), self.p0.data_ptr(), self.p1.data_ptr(),
@@ -455,7 +488,7 @@ class PTMHDevice:
     def adapt_proposal(self):
         """SamplerPTChain::AdaptProposal for every chain of the rank (T == 0 chains excepted)."""
         self.check_nan()
-        self.proposal.adapt(self.history.samples, self.history.counters, seed=self.seed,
+        (self.blocked or self.proposal).adapt(self.history.samples, self.history.counters, seed=self.seed,
                             adaptation=self.adaptations_done, chain0=self.g0,
                             max_history_samples=self.max_history_samples, adjusted_aic=self.adjusted_aic)
         # SamplerPTChain::AdaptProposal discards the history it adapted on (SampleHistory::Reset,

@@ -110,6 +110,30 @@ int bcm3_adapt_proposals(int kind, int adjusted_aic, int C, int H, int d, int km
                          const double* prior_mean, const double* prior_var, uint64_t seed, uint64_t adaptation,
                          int64_t chain0, int nthreads, int32_t* ncomp, double* weights, double* means, double* chol,
                          double* logc, int32_t* fitted);
+/* ---- variable blocks (blocking strategies, SamplerPTChain.cpp:66-77) ----
+ * The block table of one chain from a blocking strategy: BCM3_PTMH_ONE_BLOCK (one block of all d
+ * variables), BCM3_PTMH_NO_BLOCKING (one variable per block) or BCM3_PTMH_EXPLICIT_BLOCKS with
+ * block_of_variable[d] = the block of every variable (ids 0..B-1, each used at least once; NULL
+ * otherwise). Outputs: *nblocks, block_offset[d + 1], block_vars[d] (the variables grouped by block,
+ * in variable order inside a block). < 0 (message in bcm3_last_error) for an invalid partition. */
+enum { BCM3_PTMH_ONE_BLOCK = 0, BCM3_PTMH_NO_BLOCKING = 1, BCM3_PTMH_EXPLICIT_BLOCKS = 2 };
+int bcm3_build_blocks(int blocking, int d, const int32_t* block_of_variable, int32_t* nblocks,
+                      int32_t* block_offset, int32_t* block_vars);
+/* bcm3_adapt_proposals per variable block (SamplerPTChain::AdaptProposal's loop over blocks,
+ * SamplerPTChain.cpp:109-173): every block of every active chain is fitted on its own columns of
+ * the history (gathered in block order, thinned on its own, Proposal.cpp:85-114) with its
+ * variables' prior moments, by the fit routines of bcm3_adapt_proposals. Block tables per chain:
+ * nblocks[C], block_offset[C][d + 1], block_vars[C][d]. Outputs in the packed per-block layout of
+ * bcm3hip_blocks (include/bcm3hip.h): ncomp[C][d], weights[C][d][kmax], logc[C][d][kmax],
+ * means[C][kmax * d], chol[C][kmax * d * d], fitted[C][d] (may be NULL). Random numbers keyed by
+ * (seed, adaptation, chain0 + c, block); block 0 has the key of bcm3_adapt_proposals, so one block
+ * of all variables in order reproduces its output bit for bit. */
+int bcm3_adapt_proposals_blocked(int kind, int adjusted_aic, int C, int H, int d, int kmax, const float* history,
+                                 const int64_t* counts, const uint8_t* active, size_t max_history_samples,
+                                 const double* prior_mean, const double* prior_var, uint64_t seed,
+                                 uint64_t adaptation, int64_t chain0, int nthreads, const int32_t* nblocks,
+                                 const int32_t* block_offset, const int32_t* block_vars, int32_t* ncomp,
+                                 double* weights, double* means, double* chol, double* logc, int32_t* fitted);
 /* GMM::Set + LogPdf + CalculateResponsibilities (src/stats/GMM.cpp:14-45, 160-186) of K components
  * (covariances[K][d][d]) at n points x[n][d]: logpdf[n], resp[n][K], and the Cholesky factors /
  * log normalisers the device proposal state holds (chol_out[K][d][d], logc_out[K]); any output
@@ -159,11 +183,22 @@ typedef struct {
     char socket_dir[256];        /* BCM3_PTMH_TRANSPORT_SOCKET: a directory every rank's process can
                                     reach; rank r listens on <socket_dir>/bcm3_rank<r>.sock (ranks in
                                     separate processes on one host, e.g. sharing one GPU) */
+    int32_t blocking;            /* ptmhsampler.blocking_strategy: BCM3_PTMH_ONE_BLOCK (default),
+                                    BCM3_PTMH_NO_BLOCKING or BCM3_PTMH_EXPLICIT_BLOCKS. With blocks, a
+                                    mutate move is one sub-move per block (its own proposal, likelihood
+                                    launch, accept and scale adaptation; SamplerPTChain.cpp:249-307);
+                                    adaptive proposals and at most 64 variables; `speculate` is ignored */
+    const int32_t* block_of_variable; /* BCM3_PTMH_EXPLICIT_BLOCKS: the block of each of the d variables
+                                    (bcm3_build_blocks); read by bcm3_ptmh_create only */
 } bcm3_ptmh_config;
 enum { BCM3_PTMH_NUM_COUNTERS = 10 }; /* attempted / accepted mutate, attempted / accepted exchange,
                                          samples done, adaptations done, iterations, exchange rounds,
                                          likelihood launches, trajectories they evaluated (speculative
-                                         candidates included) */
+                                         candidates included). attempted mutate counts the accept
+                                         decisions taken: per mutate move one per chain with one_block;
+                                         with blocks one per T != 0 chain and block plus one per
+                                         T == 0 chain (it draws from the prior in sub-move 0 only),
+                                         while every sub-move's launch evaluates all chains */
 void bcm3_ptmh_config_default(bcm3_ptmh_config* cfg);
 int bcm3_ptmh_nccl_unique_id(void* id /* 128 bytes */);
 int bcm3_ptmh_group_create(int world, bcm3_ptmh_group** out);
@@ -190,7 +225,12 @@ int bcm3_ptmh_synchronize(bcm3_ptmh* s);
 int bcm3_ptmh_num_chains(const bcm3_ptmh* s); /* chains of this rank */
 /* host copies of the rank's chains (any may be NULL): values[C][d], llh[C], lprior[C], lpp[C] */
 int bcm3_ptmh_get_state(bcm3_ptmh* s, double* values, double* llh, double* lprior, double* lpp);
+/* mixture components in use per chain (with blocks: of each chain's block 0) */
 int bcm3_ptmh_get_components(bcm3_ptmh* s, int32_t* ncomp /* [C] */);
+/* the rank's block tables and the components of every block (any may be NULL): nblocks[C],
+ * block_offset[C][d + 1], block_vars[C][d], ncomp[C][d] (entries b < nblocks[c] in use); one_block:
+ * one block of all variables */
+int bcm3_ptmh_get_blocks(bcm3_ptmh* s, int32_t* nblocks, int32_t* block_offset, int32_t* block_vars, int32_t* ncomp);
 int bcm3_ptmh_get_counters(bcm3_ptmh* s, int64_t* out /* [BCM3_PTMH_NUM_COUNTERS] */);
 void* bcm3_ptmh_stream(const bcm3_ptmh* s);
 void bcm3_ptmh_destroy(bcm3_ptmh* s);
@@ -202,7 +242,8 @@ void bcm3_ptmh_destroy(bcm3_ptmh* s);
 int bcm3_ptmh_set_output(bcm3_ptmh* s, const char* filename, int64_t num_samples, int32_t flush_every);
 int bcm3_ptmh_flush_output(bcm3_ptmh* s);
 /* ptmhsampler.output_proposal_adaptation (SamplerPTChain.cpp:149-166): after every adaptation the
- * highest-temperature chain's proposal (group adapt<k>/block1: variable_indices, gmm_weights,
+ * highest-temperature chain's proposal (one group adapt<k>/block<i> per variable block, i from 1
+ * -- block1 alone with one_block --: variable_indices (Proposal.cpp:228-240), gmm_weights,
  * cluster<i>_mean / cluster<i>_covariance or covariance, and the fitted history from the second
  * adaptation on) is (re)written to `filename` in the NetCDFBundler layout, netCDF classic
  * (nested groups named "adapt<k>.block1.<name>"); written by the rank holding that chain. */

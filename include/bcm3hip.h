@@ -523,6 +523,58 @@ int bcm3hip_ptmh_accept_adaptive(int C, int d, const double* temps, const double
                                  double* lprior, double* llh, double* lpp, uint8_t* accept_out, uint64_t* accepted,
                                  int32_t* nan_llh, const bcm3hip_proposal* proposal, int64_t chain0, uint64_t seed,
                                  uint64_t iter, void* stream);
+/* ---- blocked Metropolis-within-Gibbs moves (blocking strategies other than one_block) ----
+ * SamplerPTChain::MutateMove's loop over variable blocks (src/sampler/SamplerPTChain.cpp:249-307):
+ * every block of a chain has its own proposal, likelihood evaluation, accept step and scale
+ * adaptation; a mutate move is max_c nblocks[c] sub-moves of propose_blocked -> one batched
+ * likelihood launch -> accept_blocked, then one bcm3hip_history_add. The block table is per chain
+ * (the kernels assume no uniformity): chain c's block b holds the variables
+ * block_vars[c][block_offset[c][b] .. block_offset[c][b + 1]), of size s_b. The proposal state is
+ * per (chain, block), packed by block_offset (o = block_offset[c][b], s = s_b):
+ *   per-block scalars   x[(c * d + b)] and x[(c * d + b) * kmax + k]
+ *   mean of component k mean[c * kmax * d + kmax * o + k * s + i]           (i < s)
+ *   factor of k         chol[c * kmax * d * d + kmax * o * d + k * s * s + i * s + j]
+ * so one block of all d variables in order has the mean / chol layout of bcm3hip_proposal.
+ * d <= 64. All pointers are device pointers. */
+typedef struct {
+    const int32_t* nblocks;      /* [C] */
+    const int32_t* block_offset; /* [C][d + 1] */
+    const int32_t* block_vars;   /* [C][d] the variables grouped by block */
+    const double* target;        /* [C][d] the block's target acceptance: 0.44 / 0.35 / 0.3 / 0.234 for a
+                                    block of 1 / 2 / 3 / more variables (Proposal.cpp:47-55) */
+    int32_t* ncomp;              /* [C][d] */
+    int32_t* selected;           /* [C][d] */
+    double* weights;             /* [C][d][kmax] */
+    double* logc;                /* [C][d][kmax] */
+    double* scale;               /* [C][d][kmax] */
+    double* ema;                 /* [C][d][kmax] */
+    double* mean;                /* [C][kmax * d] packed */
+    double* chol;                /* [C][kmax * d * d] packed */
+    uint8_t* active;             /* [C] written by propose_blocked: 1 = the chain proposed in this sub-move */
+} bcm3hip_blocks;
+/* Sub-move `submove` of iteration iter: chains with T != 0 and submove < nblocks[c] run
+ * Proposal::Update on that block's scale and draw from the block's proposal in the block's
+ * dimensions (reflected on the bounds of its variables), the other variables copied, then the
+ * Dirichlet residuals (which may lie outside the block), the log prior of the full vector and the
+ * log MH ratio over the block's coordinates; T == 0 chains draw from the prior in sub-move 0 only.
+ * Every other chain gets prop = values and active[c] = 0. `proposal` supplies kind, kmax, t_dof, the
+ * scaling constants and the bounds (its per-chain state is not read). The counter RNG's key gains
+ * the sub-move (seed + submove * 0x9E3779B97F4A7C15, normal slot = position in the block): with one
+ * block of all d variables in order, prop / lprior_prop / log_mh and the state updates are those of
+ * bcm3hip_ptmh_propose_adaptive bit for bit. */
+int bcm3hip_ptmh_propose_blocked(int C, int d, int submove, const int32_t* prior_kind, const double* prior_p0,
+                                 const double* prior_p1, const double* prior_p2, const double* temps,
+                                 const double* values, double* prop, double* lprior_prop, double* log_mh,
+                                 const bcm3hip_proposal* proposal, const bcm3hip_blocks* blocks, int64_t chain0,
+                                 uint64_t seed, uint64_t iter, void* stream);
+/* As bcm3hip_ptmh_accept_adaptive for the chains propose_blocked marked active (the others keep
+ * their state, accept_out 0): the acceptance EMA update goes to the block's state. */
+int bcm3hip_ptmh_accept_blocked(int C, int d, int submove, const double* temps, const double* prop,
+                                const double* lprior_prop, const double* llh_prop, const double* log_mh,
+                                double learning_rate, double* values, double* lprior, double* llh, double* lpp,
+                                uint8_t* accept_out, uint64_t* accepted, int32_t* nan_llh,
+                                const bcm3hip_proposal* proposal, const bcm3hip_blocks* blocks, int64_t chain0,
+                                uint64_t seed, uint64_t iter, void* stream);
 /* ---- speculative iteration pairs (SamplerPTDevice) ----
  * Iteration r+1's proposal of chain c starts from the state exchange round r+1 leaves in slot c: its
  * own state after iteration r (old = values[c], or prop[c] if accepted) or its exchange partner's
