@@ -91,6 +91,42 @@ class Blocks(C.Structure):
                                           "weights", "logc", "scale", "ema", "mean", "chol", "active")]
 
 
+INC_NVARS = 31        # BCM3HIP_INC_NVARS
+INC_WELLS = 11        # BCM3HIP_INCUCYTE_WELLS: 9 drug wells, positive control, negative control
+INC_CONC = 9          # BCM3HIP_INCUCYTE_CONCENTRATIONS
+INC_HISTORY_FULL = -1000  # BCM3HIP_INCUCYTE_HISTORY_FULL
+
+
+class IncucyteVariables(C.Structure):
+    """bcm3hip_incucyte_variables"""
+    _fields_ = [("ix", C.c_int32 * INC_NVARS)]
+
+
+class IncucyteExperiment(C.Structure):
+    """bcm3hip_incucyte_experiment (host pointers)"""
+    _fields_ = [("T", C.c_int32), ("C", C.c_int32), ("R", C.c_int32), ("seeding_density_deviation_ix", C.c_int32),
+                ("treatment_time", C.c_double), ("seeding_density", C.c_double)] + \
+               [(k, C.POINTER(C.c_double)) for k in ("time", "log10_concentration", "drug_confluence", "drug_marker",
+                                                     "pao_confluence", "pao_marker", "neg_confluence", "neg_marker",
+                                                     "ctb")]
+
+
+class IncucyteModel(C.Structure):
+    """bcm3hip_incucyte_model"""
+    _fields_ = [("d", C.c_int32), ("E", C.c_int32), ("variables", IncucyteVariables),
+                ("experiments", C.POINTER(IncucyteExperiment))]
+
+
+def incucyte_variable_names():
+    """the names of BCM3HIP_INC_* as the prior spells them"""
+    return [lib().bcm3hip_incucyte_variable_name(k).decode() for k in range(INC_NVARS)]
+
+
+def log_pdf_tnu3(x: float, mu: float, sigma: float) -> float:
+    """bcm3::LogPdfTnu3(x, mu, sigma, skip_na=True) as the host side of pk_math.h computes it"""
+    return lib().bcm3hip_log_pdf_tnu3(x, mu, sigma)
+
+
 STATS_DTYPE = np.dtype([(k, np.int32) for k in ("nst", "nfe", "nni", "nsetups", "nje", "netf", "ncfn", "nreinit")])
 
 _lib = None
@@ -153,6 +189,16 @@ def lib() -> C.CDLL:
         L.bcm3hip_assign_cells.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
         L.bcm3hip_assign_cells.restype = C.c_int
     L.bcm3hip_eval_batch_detail.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp]
+    L.bcm3hip_open_incucyte.argtypes = [C.c_int, C.POINTER(IncucyteModel), C.POINTER(vp)]
+    L.bcm3hip_open_incucyte.restype = C.c_int
+    L.bcm3hip_eval_batch_incucyte_detail.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.bcm3hip_eval_batch_incucyte_detail.restype = C.c_int
+    L.bcm3hip_eval_batch_device_counted.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
+    L.bcm3hip_eval_batch_device_counted.restype = C.c_int
+    L.bcm3hip_incucyte_variable_name.argtypes = [C.c_int]
+    L.bcm3hip_incucyte_variable_name.restype = C.c_char_p
+    L.bcm3hip_log_pdf_tnu3.argtypes = [C.c_double, C.c_double, C.c_double]
+    L.bcm3hip_log_pdf_tnu3.restype = C.c_double
     for f in ("bcm3hip_open_popk", "bcm3hip_open_analytic", "bcm3hip_open_mixture", "bcm3hip_open_expm_pk", "bcm3hip_close", "bcm3hip_set_option",
               "bcm3hip_num_variables", "bcm3hip_eval_batch", "bcm3hip_eval_batch_device",
               "bcm3hip_last_kernel_ms", "bcm3hip_eval_batch_detail"):

@@ -16,6 +16,7 @@
 
 #include "../../include/bcm3hip.h"
 #include "libm_exact.h"
+#include "incucyte_kernel.h"
 #include "popk_kernel.h"
 
 const xm::GlibcPow* bcm3_pow_tables(int* from_libm);  // libm_tables.cpp
@@ -42,7 +43,16 @@ inline bool cp_assign_lds_fits(int n) { return cp_assign_ws_bytes(n) <= 52 * 102
 
 struct bcm3hip_ctx {
     int device = 0;
-    int kind = 0;  // 1 popk, 2 analytic, 3 expm pk, 4 cell population
+    int kind = 0;  // 1 popk, 2 analytic, 3 expm pk, 4 cell population, 5 incucyte population
+    IncucyteDevModel im{};
+    // incucyte scratch, grow-only: simulated wells, CTB, per-well step counts / return codes /
+    // counters, and the step history of one chunk of items
+    double *inc_wells = nullptr, *inc_ctb = nullptr, *inc_history = nullptr;
+    int32_t *inc_steps = nullptr, *inc_codes = nullptr;
+    bcm3hip_traj_stats* inc_stats = nullptr;
+    bool inc_want_stats = false;  // the next launch also keeps each well's solver counters
+    size_t cap_inc_wells = 0, cap_inc_ctb = 0, cap_inc_history = 0, cap_inc_steps = 0, cap_inc_codes = 0,
+           cap_inc_stats = 0;
     bcm3hip::CellPopDev* cp = nullptr;
     std::vector<bcm3hip::CellPopDev*> cp_more;  // experiments 1.. of a cell-population likelihood
     double* cp_logp = nullptr;                  // their per-experiment logp / status
@@ -543,10 +553,105 @@ int bcm3hip_open_expm_pk(int device, const bcm3hip_expm_pk_model* m, bcm3hip_ctx
     return 0;
 }
 
+static const char* const kIncucyteVariableNames[BCM3HIP_INC_NVARS] = {
+    "sigma_confluence", "sigma_apoptosis_marker", "sigma_ctb", "pao_apoptosis_rate",
+    "drug_proliferation_rate_ic50", "drug_proliferation_rate_steepness", "drug_proliferation_rate_maxeffect",
+    "drug_apoptosis_rate_ic50", "drug_apoptosis_rate_steepness", "drug_apoptosis_rate_maxeffect",
+    "proliferation_rate", "apoptosis_rate", "apoptosis_duration", "apoptosis_remove_rate",
+    "log10_cell_size", "pao_apoptotic_cell_size", "apoptotic_cell_size", "debris_size", "apoptosis_marker_size",
+    "pao_apoptosis_marker_size", "debris_apoptosis_marker_size",
+    "pao_delay", "pao_effect_time", "drug_delay", "drug_effect_time",
+    "contact_inhibition_start", "contact_inhibition_max_confluence", "contact_inhibition_apoptosis_rate",
+    "starting_dead_cell_fraction", "cell_preadherence_size", "cell_adherence_time"};
+
+const char* bcm3hip_incucyte_variable_name(int which)
+{
+    return (which >= 0 && which < BCM3HIP_INC_NVARS) ? kIncucyteVariableNames[which] : nullptr;
+}
+
+int bcm3hip_open_incucyte(int device, const bcm3hip_incucyte_model* m, bcm3hip_ctx** out)
+{
+    if (!m || !out) return BCM3HIP_ERR_ARG;
+    *out = nullptr;
+    if (m->d <= 0 || m->E < 1 || !m->experiments) return BCM3HIP_ERR_MODEL;
+    for (int k = 0; k < BCM3HIP_INC_NVARS; k++)
+        if (m->variables.ix[k] < 0 || m->variables.ix[k] >= m->d) return BCM3HIP_ERR_MODEL;
+    // flatten the experiments: the first 4 replicates of every well in likelihood order
+    std::vector<IncucyteDevExperiment> exps(m->E);
+    std::vector<double> times, oc, om, octb;
+    int Tmax = 0;
+    for (int e = 0; e < m->E; e++) {
+        const bcm3hip_incucyte_experiment& x = m->experiments[e];
+        // the reference reads 9 concentrations and 4 replicates whatever the file holds
+        if (x.T < 1 || x.C < BCM3HIP_INCUCYTE_CONCENTRATIONS || x.R < BCM3HIP_INCUCYTE_REPLICATES) return BCM3HIP_ERR_MODEL;
+        if (x.seeding_density_deviation_ix < 0 || x.seeding_density_deviation_ix >= m->d) return BCM3HIP_ERR_MODEL;
+        if (!x.time || !x.log10_concentration || !x.drug_confluence || !x.drug_marker || !x.pao_confluence ||
+            !x.pao_marker || !x.neg_confluence || !x.neg_marker || !x.ctb)
+            return BCM3HIP_ERR_ARG;
+        IncucyteDevExperiment& de = exps[e];
+        de.T = x.T;
+        de.C = x.C;
+        de.sdd_ix = x.seeding_density_deviation_ix;
+        de.time_off = (int32_t)times.size();
+        de.obs_off = (int64_t)oc.size();
+        de.ctb_off = (int32_t)octb.size();
+        de.pad = 0;
+        de.treatment_time = x.treatment_time;
+        de.seeding_density = x.seeding_density;
+        for (int ci = 0; ci < BCM3HIP_INCUCYTE_CONCENTRATIONS; ci++) de.log10_conc[ci] = x.log10_concentration[ci];
+        times.insert(times.end(), x.time, x.time + x.T);
+        octb.insert(octb.end(), x.ctb, x.ctb + x.C);
+        Tmax = std::max(Tmax, (int)x.T);
+        for (int wl = 0; wl < x.C + 2; wl++)
+            for (int ti = 0; ti < x.T; ti++)
+                for (int r = 0; r < BCM3HIP_INCUCYTE_REPLICATES; r++) {
+                    if (wl < x.C) {
+                        oc.push_back(x.drug_confluence[((size_t)ti * x.C + wl) * x.R + r]);
+                        om.push_back(x.drug_marker[((size_t)ti * x.C + wl) * x.R + r]);
+                    } else {
+                        const double* cf = (wl == x.C) ? x.pao_confluence : x.neg_confluence;
+                        const double* mk = (wl == x.C) ? x.pao_marker : x.neg_marker;
+                        oc.push_back(cf[(size_t)ti * x.R + r]);
+                        om.push_back(mk[(size_t)ti * x.R + r]);
+                    }
+                }
+    }
+    bcm3hip_ctx* c = new (std::nothrow) bcm3hip_ctx();
+    if (!c) return BCM3HIP_ERR_ALLOC;
+    int r = ctx_common_init(c, device);
+    if (r == 0 && incucyte_prepare_device() != hipSuccess) r = BCM3HIP_ERR_HIP;
+    IncucyteDevModel& im = c->im;
+    im.d = m->d;
+    im.E = m->E;
+    im.Tmax = Tmax;
+    im.rtol = 1e-6;  // SetTolerance(1e-6, 1e-2), LikelihoodIncucytePopulation.cpp:131
+    im.atol = 1e-2;
+    im.ix = m->variables;
+    if (r == 0) r = upload(c, (const IncucyteDevExperiment*)exps.data(), exps.size(), &im.exps);
+    if (r == 0) r = upload(c, (const double*)times.data(), times.size(), &im.times);
+    if (r == 0) r = upload(c, (const double*)oc.data(), oc.size(), &im.obs_confluence);
+    if (r == 0) r = upload(c, (const double*)om.data(), om.size(), &im.obs_marker);
+    if (r == 0) r = upload(c, (const double*)octb.data(), octb.size(), &im.obs_ctb);
+    if (r) {
+        bcm3hip_close(c);
+        return r;
+    }
+    c->kind = 5;
+    c->d = m->d;
+    *out = c;
+    return 0;
+}
+
 int bcm3hip_close(bcm3hip_ctx* c)
 {
     if (!c) return 0;
     if (c->stream) hipSetDevice(c->device);
+    hipFree(c->inc_wells);
+    hipFree(c->inc_ctb);
+    hipFree(c->inc_history);
+    hipFree(c->inc_steps);
+    hipFree(c->inc_codes);
+    hipFree(c->inc_stats);
     if (c->cp) bcm3hip::cellpop_destroy(c->cp);
     for (auto* e : c->cp_more) bcm3hip::cellpop_destroy(e);
     hipFree(c->cp_logp);
@@ -659,6 +764,30 @@ static int auto_lanes_per_wave(size_t ntraj)
     return lpw;
 }
 
+// the incucyte step history of one launch of the well kernel stays under this many bytes; larger
+// batches run in chunks of items
+static const size_t kIncucyteHistoryBytes = (size_t)1 << 30;
+
+static int launch_incucyte_ctx(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp, int32_t* dstatus,
+                               bool want_stats, hipStream_t s, hipEvent_t e0, hipEvent_t e1, const int32_t* n_dev,
+                               hipError_t* e)
+{
+    const IncucyteDevModel& im = c->im;
+    const size_t wells_per_item = (size_t)im.E * INC_WELLS;
+    const size_t hist_per_item = wells_per_item * INC_HISTORY * 2;  // doubles
+    const size_t chunk = std::min(n, std::max<size_t>(1, kIncucyteHistoryBytes / (hist_per_item * sizeof(double))));
+    if (grow(c->inc_wells, c->cap_inc_wells, n * (size_t)im.E * INC_ARRAYS * (size_t)im.Tmax * INC_WELLS) ||
+        grow(c->inc_ctb, c->cap_inc_ctb, n * (size_t)im.E * INC_CONC) ||
+        grow(c->inc_steps, c->cap_inc_steps, n * wells_per_item) ||
+        grow(c->inc_codes, c->cap_inc_codes, n * wells_per_item) ||
+        grow(c->inc_history, c->cap_inc_history, chunk * hist_per_item) ||
+        (want_stats && grow(c->inc_stats, c->cap_inc_stats, n * wells_per_item)))
+        return BCM3HIP_ERR_ALLOC;
+    *e = launch_incucyte(im, (int64_t)n, dvalues, dlogp, dstatus, c->inc_wells, c->inc_ctb, c->inc_steps, c->inc_codes,
+                         c->inc_history, want_stats ? c->inc_stats : nullptr, (int64_t)chunk, s, e0, e1, n_dev);
+    return 0;
+}
+
 // scratch of the matrix-exponential path per launch: exps[n][n_jobs][n^2]; larger batches run in
 // chunks of evaluations so that it stays under this many bytes
 static const size_t kExpmScratchBytes = (size_t)1 << 30;
@@ -667,7 +796,7 @@ static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp
                   double* dtraj, bcm3hip_traj_stats* dstats, hipStream_t s, const int32_t* n_dev = nullptr,
                   int32_t* dsteps = nullptr)
 {
-    if ((n_dev || dsteps) && c->kind != 1) return BCM3HIP_ERR_ARG;  // PopPK launches only
+    if ((n_dev || dsteps) && c->kind != 1 && c->kind != 5) return BCM3HIP_ERR_ARG;  // PopPK / incucyte launches only
     hipError_t e;
     if (c->scratch_used && c->scratch_stream != s) HIPCHK(hipStreamWaitEvent(s, c->scratch_ev, 0));
     hipEvent_t e0 = c->ev0, e1 = c->ev1;
@@ -697,6 +826,10 @@ static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp
         e = launch_popk(c->pm, (int64_t)n, dvalues, dlogp, dstatus, c->pllh, c->tstatus, dtraj, dstats,
                         c->lanes_per_wave ? c->lanes_per_wave : auto_lanes_per_wave(n * (size_t)c->pm.P),
                         c->block_waves, c->uni_solver, s, e0, e1, c->block_lds, n_dev, dsteps, place);
+    } else if (c->kind == 5) {
+        if (n == 0) return 0;
+        int r = launch_incucyte_ctx(c, n, dvalues, dlogp, dstatus, c->inc_want_stats, s, e0, e1, n_dev, &e);
+        if (r) return r;
     } else if (c->kind == 3) {
         const size_t per_eval = (size_t)c->xm.n_jobs * (size_t)(c->xm.n * c->xm.n);
         const size_t chunk = per_eval == 0 ? n : std::max<size_t>(1, kExpmScratchBytes / (per_eval * sizeof(double)));
@@ -741,6 +874,41 @@ static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp
     return 0;
 }
 
+}  // extern "C"
+
+static int incucyte_detail(bcm3hip_ctx* c, size_t n, size_t d, const double* values, double* logp, int32_t* status,
+                           double* wells, double* ctb, int32_t* steps, int32_t* codes, bcm3hip_traj_stats* stats)
+{
+    if ((int)d != c->d || (n > 0 && (!values || !logp))) return BCM3HIP_ERR_ARG;
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    if (grow(c->values, c->cap_values, n * d)) return BCM3HIP_ERR_ALLOC;
+    if (grow(c->logp, c->cap_n, n)) return BCM3HIP_ERR_ALLOC;
+    if (grow(c->status, c->cap_status, n)) return BCM3HIP_ERR_ALLOC;
+    HIPCHK(hipMemcpyAsync(c->values, values, n * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    c->inc_want_stats = stats != nullptr;
+    int r = launch(c, n, c->values, c->logp, c->status, nullptr, nullptr, c->stream);
+    c->inc_want_stats = false;
+    if (r) return r;
+    const size_t nw = n * (size_t)c->im.E * INC_WELLS;
+    HIPCHK(hipMemcpyAsync(logp, c->logp, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, c->status, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (wells)
+        HIPCHK(hipMemcpyAsync(wells, c->inc_wells, nw * INC_ARRAYS * (size_t)c->im.Tmax * sizeof(double),
+                              hipMemcpyDeviceToHost, c->stream));
+    if (ctb)
+        HIPCHK(hipMemcpyAsync(ctb, c->inc_ctb, n * (size_t)c->im.E * INC_CONC * sizeof(double), hipMemcpyDeviceToHost,
+                              c->stream));
+    if (steps) HIPCHK(hipMemcpyAsync(steps, c->inc_steps, nw * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (codes) HIPCHK(hipMemcpyAsync(codes, c->inc_codes, nw * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (stats)
+        HIPCHK(hipMemcpyAsync(stats, c->inc_stats, nw * sizeof(bcm3hip_traj_stats), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" {
+
 int bcm3hip_eval_batch_device(bcm3hip_ctx* c, size_t n, const double* values_dev, double* logp_dev,
                               int32_t* status_dev, void* stream)
 {
@@ -754,7 +922,7 @@ int bcm3hip_eval_batch_device_counted(bcm3hip_ctx* c, size_t n_max, const int32_
                                       double* logp_dev, int32_t* status_dev, int32_t* steps_dev, void* stream)
 {
     if (!c || !n_dev || (n_max > 0 && (!values_dev || !logp_dev))) return BCM3HIP_ERR_ARG;
-    if (c->kind != 1) return BCM3HIP_ERR_ARG;
+    if (c->kind != 1 && c->kind != 5) return BCM3HIP_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     return launch(c, n_max, values_dev, logp_dev, status_dev, nullptr, nullptr, (hipStream_t)stream, n_dev, steps_dev);
 }
@@ -790,6 +958,8 @@ int bcm3hip_eval_batch_detail(bcm3hip_ctx* c, size_t n, size_t d, const double* 
 {
     if (!c || (int)d != c->d || (n > 0 && (!values || !logp))) return BCM3HIP_ERR_ARG;
     if (n == 0) return 0;
+    // incucyte: ctb as patient_llh, the simulated wells as traj, each well's solver counters as stats
+    if (c->kind == 5) return incucyte_detail(c, n, d, values, logp, status, traj, patient_llh, nullptr, nullptr, stats);
     if ((patient_llh || traj || stats) && c->kind != 1) return BCM3HIP_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     if (grow(c->values, c->cap_values, n * d)) return BCM3HIP_ERR_ALLOC;
@@ -820,6 +990,13 @@ int bcm3hip_eval_batch_detail(bcm3hip_ctx* c, size_t n, size_t d, const double* 
         HIPCHK(hipMemcpyAsync(stats, dstats, ntraj * sizeof(bcm3hip_traj_stats), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
+}
+
+int bcm3hip_eval_batch_incucyte_detail(bcm3hip_ctx* c, size_t n, size_t d, const double* values, double* logp,
+                                       int32_t* status, double* wells, double* ctb, int32_t* steps, int32_t* codes)
+{
+    if (!c || c->kind != 5) return BCM3HIP_ERR_ARG;
+    return incucyte_detail(c, n, d, values, logp, status, wells, ctb, steps, codes, nullptr);
 }
 
 int bcm3hip_eval_batch(bcm3hip_ctx* c, size_t n, size_t d, const double* values, double* logp, int32_t* status)

@@ -625,10 +625,24 @@ BDF_INL void reinit(S& s, double t0, const double (&y0)[NS])
     s.cnt.nreinit++;
 }
 
+// A model whose Jacobian depends on (t, y) declares `static constexpr bool kStateJacobian = true`
+// and supplies lin_setup_jac(t, y, jnew, gamma, inv) instead of lin_setup(gamma, inv): with jnew it
+// evaluates the Jacobian at (t, y) and keeps it (cvLsLinSys's savedJ, cvode_ls.c:1340-1400), without
+// it the kept one is reused; either way the inverse of I - gamma J follows.
+template <class Model, class = void>
+struct has_state_jacobian {
+    static constexpr bool value = false;
+};
+template <class Model>
+struct has_state_jacobian<Model, decltype((void)Model::kStateJacobian)> {
+    static constexpr bool value = Model::kStateJacobian;
+};
+
 // Newton iteration of cvNls (cvode.c:2701-2770) = SUNNonlinSolSolve_Newton
 // (sunnonlinsol_newton.c:183-322) + cvNlsResidual + cvNlsLSetup/cvLsSetup + cvLsSolve +
-// cvNlsConvTest. One residual call site. Returns true on convergence.
-template <int NS, class S, class Model>
+// cvNlsConvTest. One residual call site. Returns true on convergence. MSBJ: the steps between
+// Jacobian evaluations (CVodeSetMaxStepsBetweenJac; CVLS_MSBJ unless the caller set another).
+template <int NS, int MSBJ = CVLS_MSBJ, class S, class Model>
 BDF_INL bool newton(S& s, const Model& mdl, double rl1, int convfail, bool callSetup)
 {
     bool jbad = false;
@@ -653,13 +667,17 @@ BDF_INL bool newton(S& s, const Model& mdl, double rl1, int convfail, bool callS
             // cvNlsLSetup -> cvLsSetup (cvode_ls.c:1415-1500)
             if (jbad) convfail = CONV_BAD_J;
             const double dgamma = fabs(fdiv(s.gamma, s.gammap) - 1.0);
-            const bool jnew = (s.nst == 0) || (s.nst > s.nstlj + CVLS_MSBJ) ||
+            const bool jnew = (s.nst == 0) || (s.nst > s.nstlj + MSBJ) ||
                               ((convfail == CONV_BAD_J) && (dgamma < CVLS_DGMAX)) || (convfail == CONV_OTHER);
             if (jnew) {
                 s.cnt.nje++;
                 s.nstlj = s.nst;
             }
-            mdl.lin_setup(s.gamma, s.inv);  // A = I - gamma*J, closed-form inverse
+            // A = I - gamma*J, closed-form inverse
+            if constexpr (has_state_jacobian<Model>::value)
+                mdl.lin_setup_jac(s.tn, y, jnew, s.gamma, s.inv);
+            else
+                mdl.lin_setup(s.gamma, s.inv);
             s.cnt.nsetups++;
             s.nls_jcur = jnew;
             s.gamrat = 1.0;
@@ -783,7 +801,7 @@ BDF_INL int hin(S& s, const Model& mdl, double tout)
 
 // CVode(..., CV_ONE_STEP) (cvode.c:1006-1443) with cvStep (cvode.c:2082-2174) inlined as an
 // attempt loop with single rescale / restore / Newton call sites.
-template <int NS, class S, class Model>
+template <int NS, int MSBJ = CVLS_MSBJ, class S, class Model>
 BDF_INL int cvode_one_step(S& s, const Model& mdl, double tout, double (&yout)[NS], double& tret)
 {
     BDF_PH(0);  // driver: output interpolation, callbacks, ReInit
@@ -884,7 +902,7 @@ BDF_INL int cvode_one_step(S& s, const Model& mdl, double tout, double (&yout)[N
             constexpr int i = CI(I_);
             s.acor[i] = 0.0;
         });
-        const bool conv = newton<NS>(s, mdl, rl1, convfail, callSetup);
+        const bool conv = newton<NS, MSBJ>(s, mdl, rl1, convfail, callSetup);
         BDF_PH(5);
         if (conv) {
             // cvDoErrorTest (cvode.c:2958-3030)

@@ -6,6 +6,7 @@
 
 #include "LikelihoodDLL.h"
 #include "LikelihoodGPU.h"
+#include "LikelihoodIncucyte.h"
 #include "log.h"
 
 namespace bcm3 {
@@ -58,7 +59,7 @@ std::string option_get(const OptionsMap& vm, const std::string& key, const std::
 std::vector<std::string> LikelihoodFactory::SupportedTypes()
 {
     return {"pop_pk_trajectory", "pharmacokinetic_trajectory", "pharmaco_single", "pharmaco_population", "banana", "circular",
-            "multimodal_gaussians", "truncated_t", "dummy", "cell_population", "dll"};
+            "multimodal_gaussians", "truncated_t", "dummy", "cell_population", "incucyte_population", "dll"};
 }
 
 std::shared_ptr<Likelihood> LikelihoodFactory::CreateLikelihood(const std::string& fn,
@@ -111,10 +112,12 @@ std::shared_ptr<Likelihood> LikelihoodFactory::CreateLikelihood(const std::strin
         ll = std::make_shared<LikelihoodDummy>(sampling_threads, evaluation_threads);
     } else if (type == "cell_population") {
         ll = std::make_shared<LikelihoodCellPopulation>(sampling_threads, evaluation_threads);
+    } else if (type == "incucyte_population") {
+        ll = std::make_shared<LikelihoodIncucytePopulation>(sampling_threads, evaluation_threads);
     } else if (type == "dll") {
         ll = std::make_shared<LikelihoodDLL>(sampling_threads, evaluation_threads);
     } else {
-        LOGERROR("Unknown likelihood type \"%s\" (supported on this backend: pop_pk_trajectory, pharmacokinetic_trajectory, pharmaco_single, pharmaco_population, banana, circular, multimodal_gaussians, truncated_t, dummy, cell_population, dll)",
+        LOGERROR("Unknown likelihood type \"%s\" (supported on this backend: pop_pk_trajectory, pharmacokinetic_trajectory, pharmaco_single, pharmaco_population, banana, circular, multimodal_gaussians, truncated_t, dummy, cell_population, incucyte_population, dll)",
                  type.c_str());
         return ll;
     }

@@ -411,6 +411,25 @@ Json NcClassicRead(const std::string& filename)
         grp.type = Json::Object;
         grp.obj[leaf] = std::move(var);
     }
+    // a group's numeric attributes (the reference's GetAttribute, e.g. treatment_time of an Incucyte
+    // experiment) are global attributes "g.name" here: scalars of the group, unless a variable has
+    // the name
+    for (auto& a : h.gattrs) {
+        if (a.type == NcChar || a.nums.size() != 1 || a.name.rfind('.') == std::string::npos) continue;
+        std::string g, leaf;
+        split(a.name, g, leaf);
+        Json& grp = doc.obj[g];
+        grp.type = Json::Object;
+        if (grp.obj.count(leaf)) continue;
+        Json var, dims, data;
+        var.type = Json::Object;
+        dims.type = Json::Array;
+        data.type = Json::Number;
+        data.num = a.nums[0];
+        var.obj["dims"] = dims;
+        var.obj["data"] = data;
+        grp.obj[leaf] = std::move(var);
+    }
     return doc;
 }
 

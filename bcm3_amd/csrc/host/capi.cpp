@@ -13,6 +13,7 @@
 
 #include "capi_internal.h"
 #include "LikelihoodCellPopulation.h"
+#include "LikelihoodIncucyte.h"
 
 extern "C" {
 
@@ -123,6 +124,26 @@ int bcm3_likelihood_expm_pk_model(const bcm3_likelihood* h, void* model)
         return 0;
     }
     return -2;
+}
+
+int bcm3_likelihood_incucyte_model(const bcm3_likelihood* h, void* model)
+{
+    if (!h || !model) return -1;
+    if (auto* p = dynamic_cast<bcm3::LikelihoodIncucytePopulation*>(h->ll.get())) {
+        *(bcm3hip_incucyte_model*)model = p->GetDeviceModel();
+        return 0;
+    }
+    return -2;
+}
+
+int bcm3_likelihood_incucyte_detail(bcm3_likelihood* h, size_t n, const double* values, double* logp, int32_t* status,
+                                    double* wells, double* ctb, int32_t* steps, int32_t* codes)
+{
+    if (!h || !h->ll) return -1;
+    auto* p = dynamic_cast<bcm3::LikelihoodIncucytePopulation*>(h->ll.get());
+    if (!p || !p->Context()) return -2;
+    return bcm3hip_eval_batch_incucyte_detail(p->Context(), n, p->GetNumVariables(), values, logp, status, wells, ctb,
+                                              steps, codes);
 }
 
 void bcm3_likelihood_destroy(bcm3_likelihood* h) { delete h; }

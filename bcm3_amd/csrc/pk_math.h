@@ -85,4 +85,14 @@ BDF_INL double log_pdf_tnu4(double x, double mu, double sigma)
     return -0.9808292530117262 - 2.5 * xm::lib<COLD>::log1p(0.25 * xn * xn) - xm::lib<COLD>::log(sigma);
 }
 
+// LogPdfTnu3(x, mu, sigma, skip_na = true) (src/utils/ProbabilityDistributions.cpp:206-214): a NaN
+// observation contributes 0. Host and device (bcm3hip_log_pdf_tnu3 exposes the host side to tests).
+template <bool COLD = false>
+__host__ __device__ __forceinline__ double log_pdf_tnu3(double x, double mu, double sigma)
+{
+    if (x != x) return 0.0;
+    double xn = (x - mu) / sigma;
+    return -1.0008888496235098 - 2.0 * xm::lib<COLD>::log1p(0.333333333333333333 * xn * xn) - xm::lib<COLD>::log(sigma);
+}
+
 }  // namespace bcm3hip

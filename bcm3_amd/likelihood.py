@@ -31,6 +31,8 @@ def lib() -> C.CDLL:
     L.bcm3_likelihood_create_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(vp)]
     L.bcm3_likelihood_popk_model.argtypes = [vp, C.POINTER(_hip.PopPKModel)]
     L.bcm3_likelihood_expm_pk_model.argtypes = [vp, C.POINTER(_hip.ExpmPKModel)]
+    L.bcm3_likelihood_incucyte_model.argtypes = [vp, C.POINTER(_hip.IncucyteModel)]
+    L.bcm3_likelihood_incucyte_detail.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
     L.bcm3_likelihood_destroy.argtypes = [vp]
     L.bcm3_likelihood_destroy.restype = None
     L.bcm3_likelihood_num_variables.argtypes = [vp]
@@ -102,6 +104,46 @@ class Likelihood:
         if r != 0:
             _err("bcm3_likelihood_expm_pk_model", r)
         return m
+
+    def incucyte_model(self) -> dict:
+        """incucyte_population: the model handed to the device as arrays -- per experiment the
+        observation times, log10 concentrations, observed wells and CTB, treatment time and seeding
+        density, plus the index of every named variable (bcm3_likelihood_incucyte_model)."""
+        m = _hip.IncucyteModel()
+        r = lib().bcm3_likelihood_incucyte_model(self.h, C.byref(m))
+        if r != 0:
+            _err("bcm3_likelihood_incucyte_model", r)
+        exps = []
+        for k in range(m.E):
+            x = m.experiments[k]
+            T, Cn, R = x.T, x.C, x.R
+            arr = lambda p, *shape: np.ctypeslib.as_array(p, shape=shape).copy()  # noqa: E731
+            exps.append(dict(T=T, C=Cn, R=R, seeding_density_deviation_ix=x.seeding_density_deviation_ix,
+                             treatment_time=x.treatment_time, seeding_density=x.seeding_density,
+                             time=arr(x.time, T), log10_concentration=arr(x.log10_concentration, Cn),
+                             drug_confluence=arr(x.drug_confluence, T, Cn, R), drug_marker=arr(x.drug_marker, T, Cn, R),
+                             pao_confluence=arr(x.pao_confluence, T, R), pao_marker=arr(x.pao_marker, T, R),
+                             neg_confluence=arr(x.neg_confluence, T, R), neg_marker=arr(x.neg_marker, T, R),
+                             ctb=arr(x.ctb, Cn)))
+        names = _hip.incucyte_variable_names()
+        return dict(d=m.d, E=m.E, variables={n: int(m.variables.ix[k]) for k, n in enumerate(names)}, experiments=exps)
+
+    def incucyte_detail(self, values, E: int, Tmax: int) -> dict:
+        """incucyte_population: one batch with the simulated wells (the reference's GetSimulated*
+        surface): logp [n], status [n], wells [n, E, 5, Tmax, 11] (cell count, apoptotic count, debris,
+        confluence, marker; columns 9 drug wells, positive control, negative control), ctb [n, E, 9],
+        steps and codes [n, E, 11] (bcm3hip_eval_batch_incucyte_detail)."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        out = dict(logp=np.empty(n), status=np.empty(n, dtype=np.int32),
+                   wells=np.empty((n, E, 5, Tmax, _hip.INC_WELLS)), ctb=np.empty((n, E, _hip.INC_CONC)),
+                   steps=np.empty((n, E, _hip.INC_WELLS), dtype=np.int32),
+                   codes=np.empty((n, E, _hip.INC_WELLS), dtype=np.int32))
+        r = lib().bcm3_likelihood_incucyte_detail(self.h, n, v.ctypes.data, *(out[k].ctypes.data for k in
+                                                  ("logp", "status", "wells", "ctb", "steps", "codes")))
+        if r != 0:
+            _err("bcm3_likelihood_incucyte_detail", r)
+        return out
 
     def generated_code(self) -> str:
         """cell_population: the generated_derivative body this likelihood compiled (SBMLModel::GenerateCode)."""

@@ -41,6 +41,13 @@ int bcm3_likelihood_popk_model(const bcm3_likelihood* ll, void* model);
  * PharmacoLikelihoodSingle::PostInitialize (.cpp:78-147), into a bcm3hip_expm_pk_model. Returns
  * -2 for other likelihood types. */
 int bcm3_likelihood_expm_pk_model(const bcm3_likelihood* ll, void* model);
+/* The model an incucyte_population likelihood hands to the device: the experiments of
+ * <drug>/<cell_line> in drug_response_data.nc and the index of every named variable, into a
+ * bcm3hip_incucyte_model. Returns -2 for other likelihood types. */
+int bcm3_likelihood_incucyte_model(const bcm3_likelihood* ll, void* model);
+/* bcm3hip_eval_batch_incucyte_detail on the likelihood's context (-2: another type, or no device) */
+int bcm3_likelihood_incucyte_detail(bcm3_likelihood* ll, size_t n, const double* values, double* logp, int32_t* status,
+                                    double* wells, double* ctb, int32_t* steps, int32_t* codes);
 /* cell_population: the generated_derivative body (SBMLModel::GenerateCode, src/sbml/SBMLModel.cpp:
  * 291-367) this likelihood compiled; returns its length (buf may be NULL), < 0 for other types */
 int bcm3_likelihood_generated_code(const bcm3_likelihood* ll, char* buf, size_t buflen);

@@ -328,6 +328,69 @@ typedef struct {
     int32_t nsteps;
 } bcm3hip_cell_record;
 
+/* ---- incucyte_population likelihood (src/likelihoods/LikelihoodIncucytePopulation.cpp) ---------
+ * Cell growth and drug-induced apoptosis in Incucyte wells: per experiment 11 wells (9 drug
+ * concentrations on an S-curve, the PAO positive control, the negative control), each a 3-state
+ * (live, apoptotic, debris) stiff ODE whose removal term reads the apoptotic count
+ * apoptosis_duration ago from the solve's own history (CVODESolverDelay, src/odecommon/
+ * CVODESolverDelay.cpp), with stop times where the drug effect starts and where it is complete.
+ * The reference build's shape is compiled in: exactly 9 simulated concentrations, 4 replicates,
+ * the PAO control on, no combination drugs. Sampled values are read untransformed. */
+enum {
+    BCM3HIP_INCUCYTE_CONCENTRATIONS = 9,
+    BCM3HIP_INCUCYTE_REPLICATES = 4,
+    BCM3HIP_INCUCYTE_WELLS = 11,     /* columns of the simulated arrays: 9 drug wells, PAO, negative control */
+    BCM3HIP_INCUCYTE_HISTORY = 2000  /* CVODESolverDelay's max_steps: accepted steps kept per solve */
+};
+/* Per-well return code besides CVODE's own (0 success, < 0 CVODE's CV_* failure code): the history
+ * already held BCM3HIP_INCUCYTE_HISTORY entries when another step had to be stored. */
+#define BCM3HIP_INCUCYTE_HISTORY_FULL (-1000)
+/* the variables the S-curve path looks up by name, in this order (bcm3hip_incucyte_variable_name) */
+enum {
+    BCM3HIP_INC_SIGMA_CONFLUENCE = 0, BCM3HIP_INC_SIGMA_APOPTOSIS_MARKER, BCM3HIP_INC_SIGMA_CTB,
+    BCM3HIP_INC_PAO_APOPTOSIS_RATE,
+    BCM3HIP_INC_DRUG_PROLIFERATION_RATE_IC50, BCM3HIP_INC_DRUG_PROLIFERATION_RATE_STEEPNESS,
+    BCM3HIP_INC_DRUG_PROLIFERATION_RATE_MAXEFFECT,
+    BCM3HIP_INC_DRUG_APOPTOSIS_RATE_IC50, BCM3HIP_INC_DRUG_APOPTOSIS_RATE_STEEPNESS,
+    BCM3HIP_INC_DRUG_APOPTOSIS_RATE_MAXEFFECT,
+    BCM3HIP_INC_PROLIFERATION_RATE, BCM3HIP_INC_APOPTOSIS_RATE, BCM3HIP_INC_APOPTOSIS_DURATION,
+    BCM3HIP_INC_APOPTOSIS_REMOVE_RATE,
+    BCM3HIP_INC_LOG10_CELL_SIZE, BCM3HIP_INC_PAO_APOPTOTIC_CELL_SIZE, BCM3HIP_INC_APOPTOTIC_CELL_SIZE,
+    BCM3HIP_INC_DEBRIS_SIZE, BCM3HIP_INC_APOPTOSIS_MARKER_SIZE, BCM3HIP_INC_PAO_APOPTOSIS_MARKER_SIZE,
+    BCM3HIP_INC_DEBRIS_APOPTOSIS_MARKER_SIZE,
+    BCM3HIP_INC_PAO_DELAY, BCM3HIP_INC_PAO_EFFECT_TIME, BCM3HIP_INC_DRUG_DELAY, BCM3HIP_INC_DRUG_EFFECT_TIME,
+    BCM3HIP_INC_CONTACT_INHIBITION_START, BCM3HIP_INC_CONTACT_INHIBITION_MAX_CONFLUENCE,
+    BCM3HIP_INC_CONTACT_INHIBITION_APOPTOSIS_RATE,
+    BCM3HIP_INC_STARTING_DEAD_CELL_FRACTION, BCM3HIP_INC_CELL_PREADHERENCE_SIZE, BCM3HIP_INC_CELL_ADHERENCE_TIME,
+    BCM3HIP_INC_NVARS
+};
+typedef struct {
+    int32_t ix[BCM3HIP_INC_NVARS]; /* index of each named variable in the prior, all in [0, d) */
+} bcm3hip_incucyte_variables;
+/* One <drug>/<cell_line>/experiment<k> group of drug_response_data.nc (Initialize, .cpp:56-122) */
+typedef struct {
+    int32_t T;                      /* time points (>= 1) */
+    int32_t C;                      /* drug concentrations in the data (>= 9) */
+    int32_t R;                      /* replicates in the data (>= 4; the first 4 are read) */
+    int32_t seeding_density_deviation_ix; /* seeding_density_deviation_<k> */
+    double treatment_time, seeding_density;
+    const double* time;             /* [T] */
+    const double* log10_concentration; /* [C] */
+    const double* drug_confluence;  /* [T][C][R], NaN = not observed */
+    const double* drug_marker;      /* [T][C][R] */
+    const double* pao_confluence;   /* [T][R] positive control */
+    const double* pao_marker;       /* [T][R] */
+    const double* neg_confluence;   /* [T][R] negative control */
+    const double* neg_marker;       /* [T][R] */
+    const double* ctb;              /* [C] cell_titer_blue_norm */
+} bcm3hip_incucyte_experiment;
+typedef struct {
+    int32_t d;                      /* sampled variables */
+    int32_t E;                      /* experiments (>= 1) */
+    bcm3hip_incucyte_variables variables;
+    const bcm3hip_incucyte_experiment* experiments; /* [E] */
+} bcm3hip_incucyte_model;
+
 typedef struct bcm3hip_ctx bcm3hip_ctx;
 
 /* Per-trajectory solver counters (parity/diagnostics), one record per (item, patient). */
@@ -393,6 +456,26 @@ int bcm3hip_cellpop_precompile(const bcm3hip_cellpop_model* model);
  * where that evaluation stopped enqueueing. */
 int bcm3hip_cellpop_cells(bcm3hip_ctx* ctx, size_t item, int32_t* count, bcm3hip_cell_record* records,
                           double* values, double* end_y);
+/* incucyte_population: one launch solves every well of every experiment of every item, a second
+ * small one adds the likelihood terms per item in the reference's order. Per-item status 1 when any
+ * well's solve fails (a CVODE failure, the CV_ILL_INPUT of a stop time at or before the start, a
+ * full history): logp = -inf. The step history (2000 x 16 B per well) lives in device memory, sized
+ * from the batch and grown on demand. No speculative pairs (bcm3hip_eval_batch_device_counted takes
+ * the device-side count; steps_dev is left unwritten). */
+int bcm3hip_open_incucyte(int device, const bcm3hip_incucyte_model* model, bcm3hip_ctx** out);
+/* bcm3::LogPdfTnu3(x, mu, sigma, skip_na = true) as the incucyte kernel's host side computes it
+ * (pk_math.h): 0 for a NaN observation. Host only, no device needed. */
+double bcm3hip_log_pdf_tnu3(double x, double mu, double sigma);
+/* name of variable BCM3HIP_INC_* as the prior spells it (NULL out of range); host only */
+const char* bcm3hip_incucyte_variable_name(int which);
+/* Parity/diagnostic batch of an incucyte context (host buffers, any output but logp may be NULL):
+ * the reference's GetSimulated* surface. wells[n][E][5][Tmax][11]: cell count, apoptotic count,
+ * debris, confluence and apoptosis marker per time point (Tmax = the longest experiment; rows past
+ * an experiment's T and wells whose solve failed are NaN) with the columns 9 drug wells, positive
+ * control, negative control; ctb[n][E][9]; steps[n][E][11] successful one-step calls of each well's
+ * solve; codes[n][E][11] its return code (0, CVODE's CV_* code, BCM3HIP_INCUCYTE_HISTORY_FULL). */
+int bcm3hip_eval_batch_incucyte_detail(bcm3hip_ctx* ctx, size_t n, size_t d, const double* values, double* logp,
+                                       int32_t* status, double* wells, double* ctb, int32_t* steps, int32_t* codes);
 int bcm3hip_close(bcm3hip_ctx* ctx);
 int bcm3hip_set_option(bcm3hip_ctx* ctx, int option, int64_t value);
 int bcm3hip_num_variables(const bcm3hip_ctx* ctx);
@@ -744,7 +827,9 @@ int bcm3hip_nccl_exchange(void* comm, int n_send, const double* const* send, con
 
 /* Parity/diagnostic batch (host buffers, any output may be NULL):
  * patient_llh[n*P], traj[n*P*N*T] (states at output times, NaN where not simulated),
- * stats[n*P]. PopPK contexts only. */
+ * stats[n*P]. PopPK contexts; for an incucyte context patient_llh is ctb[n][E][9], traj is
+ * wells[n][E][5][Tmax][11] and stats[n][E][11] the solver counters of each well (see
+ * bcm3hip_eval_batch_incucyte_detail, which also returns the step counts and return codes). */
 int bcm3hip_eval_batch_detail(bcm3hip_ctx* ctx, size_t n, size_t d, const double* values, double* logp,
                               int32_t* status, double* patient_llh, double* traj, bcm3hip_traj_stats* stats);
 
