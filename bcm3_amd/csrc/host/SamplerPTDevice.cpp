@@ -521,13 +521,15 @@ struct SamplerPTDevice::Impl {
     const int32_t* BlockVars(int64_t c, int b) const { return &bl_vars[(size_t)(c * d + BlockOffset(c, b))]; }
 
     // the table from the blocking strategy, the same for every chain of the rank (a strategy that
-    // clusters each chain's history would fill the per-chain rows differently), and the prior-moment
+    // clusters each chain's history would fill the per-chain rows differently), checked on the host
+    // before anything is allocated or launched; SetupBlocks then uploads it with the prior-moment
     // proposal of every block: the reference adapts once on an empty history in
     // SamplerPTChain::Initialize (SamplerPTChain.cpp:95), which is InitProposal's state per block
-    bool SetupBlocks()
+    bool BuildBlockTable()
     {
-        if (!adaptive || d > 64) {
-            LOGERROR("SamplerPTDevice: variable blocks need an adaptive proposal and at most 64 variables (%d)", d);
+        if (!adaptive || d > BCM3HIP_BLOCKED_MAX_D) {
+            LOGERROR("SamplerPTDevice: variable blocks need an adaptive proposal and at most %d variables (%d)",
+                     BCM3HIP_BLOCKED_MAX_D, d);
             return false;
         }
         if (cfg.blocking == BCM3_PTMH_EXPLICIT_BLOCKS && (int)cfg.block_of_variable.size() != d) {
@@ -546,11 +548,25 @@ struct SamplerPTDevice::Impl {
             std::copy(off.begin(), off.end(), bl_off.begin() + c * (d + 1));
             std::copy(vars.begin(), vars.end(), bl_vars.begin() + c * d);
         }
+        // a block is one wavefront of the propose kernels
+        for (int64_t c = 0; c < C; c++)
+            for (int b = 0; b < bl_n[c]; b++)
+                if (BlockSize(c, b) > BCM3HIP_BLOCK_MAX_SIZE) {
+                    LOGERROR("SamplerPTDevice: block %d has %d variables; a block holds at most %d (one_block moves all "
+                             "variables at once)", b, BlockSize(c, b), BCM3HIP_BLOCK_MAX_SIZE);
+                    return false;
+                }
         max_blocks = nb;
         sub_decisions.assign(max_blocks, 0);
         for (int m = 0; m < max_blocks; m++)
             for (int64_t c = 0; c < C; c++)
                 if (temps_host[c] == 0.0 ? m == 0 : m < bl_n[c]) sub_decisions[m]++;
+        return true;
+    }
+
+    // the device side of the table (BuildBlockTable has run)
+    bool SetupBlocks()
+    {
         const int64_t K = kmax;
         if (!b_nblocks.alloc(C) || !b_offset.alloc(C * (d + 1)) || !b_vars.alloc(C * d) || !b_target.alloc(C * d) ||
             !b_ncomp.alloc(C * d) || !b_selected.alloc(C * d) || !b_weights.alloc(C * d * K) ||
@@ -1327,10 +1343,17 @@ bool SamplerPTDevice::Initialize(std::shared_ptr<Likelihood> ll, const std::vect
                 return false;
             }
     }
+    if (cfg.blocking != BCM3_PTMH_ONE_BLOCK) {
+        if (cfg.blocking != BCM3_PTMH_NO_BLOCKING && cfg.blocking != BCM3_PTMH_EXPLICIT_BLOCKS) {
+            LOGERROR("SamplerPTDevice: unknown blocking strategy %d", cfg.blocking);
+            return false;
+        }
+    }
     // Proposal::Initialize (Proposal.cpp:45-53)
     s.target = (s.d == 1) ? 0.44 : (s.d == 2) ? 0.35 : (s.d == 3) ? 0.3 : 0.234;
     const auto ladder = TemperatureLadder(s.Ctot, cfg.temperature_power, cfg.temperature_max);
     s.temps_host.assign(ladder.begin() + s.g0, ladder.begin() + s.g0 + s.C);
+    if (cfg.blocking != BCM3_PTMH_ONE_BLOCK && !s.BuildBlockTable()) return false;
 
     if (stream) {
         s.stream = stream;
@@ -1401,10 +1424,6 @@ bool SamplerPTDevice::Initialize(std::shared_ptr<Likelihood> ll, const std::vect
     s.P.work = s.work.p;
     if (!s.InitProposal()) return false;
     if (cfg.blocking != BCM3_PTMH_ONE_BLOCK) {
-        if (cfg.blocking != BCM3_PTMH_NO_BLOCKING && cfg.blocking != BCM3_PTMH_EXPLICIT_BLOCKS) {
-            LOGERROR("SamplerPTDevice: unknown blocking strategy %d", cfg.blocking);
-            return false;
-        }
         s.blocked = true;
         if (!s.SetupBlocks()) return false;
     }

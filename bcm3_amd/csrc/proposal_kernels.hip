@@ -16,6 +16,7 @@
 //   ptmh_propose_blocked_kernel / ptmh_accept_blocked_kernel   the same moves per variable block
 //                                 (MutateMove's loop over blocks, SamplerPTChain.cpp:249-307) for
 //                                 blocking strategies other than one_block (bcm3hip_blocks);
+//   ptmh_propose_blocked_wide_kernel   the blocked propose for 64 < d <= BCM3HIP_BLOCKED_MAX_D;
 //   history_add_kernel            SampleHistory::AddSample (SampleHistory.cpp:32-45) after a mutate
 //                                 move (SamplerPTChain.cpp:309) or an exchange move (:374-379).
 //
@@ -943,6 +944,241 @@ __global__ void __launch_bounds__(64) ptmh_propose_blocked_kernel(
     }
 }
 
+// wave_seq_sum continued: acc + x_0 + ... + x_{n-1} in lane order (uniform result)
+__device__ __forceinline__ double wave_seq_sum_from(double acc, int n, double x)
+{
+    for (int i = 0; i < n; i++) acc += lane_bcast(x, i);
+    return acc;
+}
+
+// ptmh_propose_blocked_kernel for 64 < d <= BCM3HIP_BLOCKED_MAX_D: one wavefront per chain and the
+// same two index spaces. The block (s <= 64) stays lane j = position j with the arithmetic, helpers
+// and RNG slots of the kernel above, so a block's proposal does not depend on the variables outside
+// it. The full vector is staged in LDS (xs, 8 KB): variable i is handled by lane i % 64 in pass
+// i / 64 -- the copy, the T = 0 prior draws (slot = variable), the scatter of the block's new
+// coordinates (a block's variables may lie in any pass), the Dirichlet sums, which read xs in
+// variable order across pass boundaries, and the log prior, summed left to right over 0 .. d-1
+// (wave_seq_sum continued from pass to pass). Every branch around a barrier is wave-uniform.
+__global__ void __launch_bounds__(64) ptmh_propose_blocked_wide_kernel(
+    int C, int d, int m, const int32_t* __restrict__ kind, const double* __restrict__ p0, const double* __restrict__ p1,
+    const double* __restrict__ p2, const double* __restrict__ temps, const double* __restrict__ values,
+    double* __restrict__ prop, double* __restrict__ lprior_prop, double* __restrict__ log_mh, bcm3hip_proposal P,
+    bcm3hip_blocks B, int64_t chain0, uint64_t seed0, uint64_t iter)
+{
+    __shared__ double xs[BCM3HIP_BLOCKED_MAX_D];
+    const int c = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    if (c >= C || d > BCM3HIP_BLOCKED_MAX_D) return;
+    const int lane = threadIdx.x & 63;
+    const int npass = (d + 63) >> 6;
+    const uint64_t gc = (uint64_t)(chain0 + c);
+    const uint64_t seed = submove_seed(seed0, m);
+    const double* vrow = values + (int64_t)c * d;
+    double lmh = 0.0;
+    bool mine = false;
+    for (int p = 0; p < npass; p++) {
+        const int i = p * 64 + lane;
+        if (i < d) {
+            xs[i] = vrow[i];
+            mine = mine || kind[i] == BCM3HIP_PRIOR_DIRICHLET;
+        }
+    }
+    const bool dir = __builtin_amdgcn_ballot_w64(mine) != 0;
+    __syncthreads();
+    const double T = temps[c];
+    int nb = B.nblocks[c];
+    nb = (nb < 0) ? 0 : ((nb > d) ? d : nb);
+    const bool active = (T == 0.0) ? (m == 0) : (m < nb);
+    if (lane == 0) B.active[c] = active ? 1 : 0;
+    if (active && T == 0.0) {
+        for (int p = 0; p < npass; p++) {
+            const int i = p * 64 + lane;
+            if (i < d) xs[i] = prior::sample(kind[i], p0[i], p1[i], p2[i], seed, iter, gc, i);
+        }
+        __syncthreads();
+        if (dir) {
+            for (int f = 0; f < d; f++) {
+                if (kind[f] != BCM3HIP_PRIOR_DIRICHLET || (int)p1[f] != f) continue;
+                const int l = prior::dirichlet_last(d, kind, p1, f);
+                double sum = 0.0;
+                for (int j = f; j <= l; j++) sum += xs[j];
+                const double inv = 1.0 / sum;
+                __syncthreads();
+                for (int i = f + lane; i <= l; i += 64) xs[i] *= inv;
+                __syncthreads();
+            }
+        }
+    } else if (active) {
+        // the block: offset o, size s (clamped into the table and to the wavefront, so a malformed
+        // table cannot index outside the chain's rows)
+        int o = B.block_offset[(int64_t)c * (d + 1) + m];
+        int s = B.block_offset[(int64_t)c * (d + 1) + m + 1] - o;
+        o = (o < 0) ? 0 : ((o > d - 1) ? d - 1 : o);
+        s = (s < 1) ? 1 : ((s > d - o) ? d - o : s);
+        s = (s > 64) ? 64 : s;
+        const bool onb = lane < s;
+        const int lb = onb ? lane : 0;
+        int var = B.block_vars[(int64_t)c * d + o + lb];
+        var = (var < 0) ? 0 : ((var > d - 1) ? d - 1 : var);
+        const double curb = vrow[var];
+        const int Km = P.kmax;
+        const int64_t cb = (int64_t)c * d + m;
+        int K = (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) ? B.ncomp[cb] : 1;
+        K = (K < 1) ? 1 : ((K > Km) ? Km : K);
+        double* scale = B.scale + cb * Km;
+        const double* ema = B.ema + cb * Km;
+        const double* logc = B.logc + cb * Km;
+        const double* w = B.weights + cb * Km;
+        const double* mean = B.mean + (int64_t)c * Km * d + (int64_t)Km * o;
+        const double* chol = B.chol + (int64_t)c * Km * d * d + (int64_t)Km * o * d;
+        const double slr = P.scaling_learning_rate;
+        const double target = B.target[cb];
+        int sel;
+        double rf = 0.0;
+        int upd = -1;
+        double sc = 0.0;
+        if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
+            const int last = B.selected[cb];
+            if (last != -1) {
+                const double lrate = 1.0 + u01(rng_key(seed, iter, gc, rng::KEY_UPDATE)) * slr * K;
+                sc = scale[last];
+                const double e = ema[last];
+                if (e < target / (1.0 - slr)) {
+                    sc /= lrate;
+                    sc = (sc > 1e-4) ? sc : 1e-4;
+                } else if (e > (1 + slr) * target) {
+                    sc *= lrate;
+                    sc = (sc < 10.0) ? sc : 10.0;
+                }
+                if (lane == 0) scale[last] = sc;
+                upd = last;
+            }
+            rf = wave_responsibilities(K, s, curb, mean, chol, logc, w, lane);
+            const double u = u01(rng_key(seed, iter, gc, rng::KEY_SELECT));
+            double acc = 0.0;
+            sel = K - 1;
+            for (int k = 0; k < K; k++) {
+                acc += lane_bcast(rf, k);
+                if (u < acc) {
+                    sel = k;
+                    break;
+                }
+            }
+        } else {
+            const double lrate = 1.0 + u01(rng_key(seed, iter, gc, rng::KEY_UPDATE)) * slr;
+            sc = scale[0];
+            const double e = ema[0];
+            if (e < 0.952381 * target) {
+                sc /= lrate;
+                sc = (sc > 1e-4) ? sc : 1e-4;
+            } else if (e > 1.05 * target) {
+                sc *= lrate;
+                sc = (sc < 10.0) ? sc : 10.0;
+            }
+            if (lane == 0) scale[0] = sc;
+            upd = 0;
+            sel = 0;
+        }
+        double t_scale = 1.0;
+        if (P.t_dof > 0.0) {
+            const double wg = gamma_draw(0.5 * P.t_dof, 0.5 * P.t_dof, seed, iter, gc);
+            t_scale = 1.0 / sqrt(wg);
+        }
+        const double* Ls = chol + (int64_t)sel * s * s + (int64_t)lb * s;
+        const double z = normal01(seed, iter, gc, lb);
+        const double f = t_scale * ((sel == upd) ? sc : scale[sel]);
+        double x = 0.0;
+        for (int j = 0; j < s; j++) {
+            const double zj = lane_bcast(z, j);
+            const double a = x + Ls[j] * zj;
+            x = (j <= lane) ? a : x;
+        }
+        const double newb = reflect(x * f + curb, P.lower[var], P.upper[var]);
+        if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE && s <= 16) {
+            double r = 0.0, qv = 0.0;
+            for (int k = 0; k < K; k++) {
+                const double sk = (k == upd) ? sc : scale[k];
+                const double ta0 = onb ? newb - mean[k * s + lane] : 0.0;
+                const double tb0 = onb ? (newb - curb) / sk : 0.0;
+                double ta, tb;
+                wave_lower_solve2_reg<16>(s, chol + (int64_t)k * s * s + (int64_t)lb * s, ta0, tb0, lane, ta, tb);
+                const double rk = (logc[k] - 0.5 * wave_seq_sum(s, onb ? ta * ta : 0.0)) + log(w[k]);
+                r = (lane == k) ? rk : r;
+                const double q = 0.5 * wave_seq_sum(s, onb ? tb * tb : 0.0);
+                qv = (lane == k) ? q : qv;
+            }
+            double lsum;
+            const double rr = wave_normalize_resp(K, r, lsum);
+            double fwd = -INFINITY, rev = -INFINITY;
+            for (int k = 0; k < K; k++) {
+                const double sk = (k == upd) ? sc : scale[k];
+                const double base = -log(sk * sk) + logc[k];
+                const double q = lane_bcast(qv, k);
+                fwd = logsum2(fwd, (base - q) + log(lane_bcast(rf, k)));
+                rev = logsum2(rev, (base - q) + log(lane_bcast(rr, k)));
+            }
+            lmh = rev - fwd;
+        } else if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
+            const double rr = wave_responsibilities(K, s, newb, mean, chol, logc, w, lane);
+            double fwd = -INFINITY, rev = -INFINITY;
+            for (int k = 0; k < K; k++) {
+                const double sk = (k == upd) ? sc : scale[k];
+                const double t0 = onb ? (newb - curb) / sk : 0.0;
+                const double t = wave_lower_solve(s, chol + (int64_t)k * s * s + (int64_t)lb * s, t0, lane);
+                const double base = -log(sk * sk) + logc[k];
+                const double q = 0.5 * wave_seq_sum(s, onb ? t * t : 0.0);
+                fwd = logsum2(fwd, (base - q) + log(lane_bcast(rf, k)));
+                rev = logsum2(rev, (base - q) + log(lane_bcast(rr, k)));
+            }
+            lmh = rev - fwd;
+        }
+        // the block's new coordinates into the full vector (var is clamped to [0, d - 1]), the rest unchanged
+        if (onb) xs[var] = newb;
+        __syncthreads();
+        if (dir) {
+            // Dirichlet residual after the MH ratio of the unmodified proposal (SamplerPTChain.cpp:270-278);
+            // the group may straddle passes and the residual may lie outside the block
+            for (int f2 = 0; f2 < d; f2++) {
+                if (kind[f2] != BCM3HIP_PRIOR_DIRICHLET || (int)p1[f2] != f2) continue;
+                const int l = prior::dirichlet_last(d, kind, p1, f2);
+                double sum = 0.0;
+                for (int j = f2; j < l; j++) sum += xs[j];
+                __syncthreads();
+                if (lane == 0) xs[l] = 1.0 - sum;
+                __syncthreads();
+            }
+        }
+        if (lane == 0) B.selected[cb] = sel;
+    }
+    double lp = 0.0;
+    if (dir) {
+        for (int f = 0; f < d; f++)
+            if (kind[f] == BCM3HIP_PRIOR_DIRICHLET && (int)p1[f] == f)
+                lp += prior::dirichlet_log_pdf(f, prior::dirichlet_last(d, kind, p1, f), p0, p2[f],
+                                               [&](int j) { return xs[j]; });
+    }
+    for (int p = 0; p < npass; p++) {
+        const int i = p * 64 + lane;
+        const bool on = i < d;
+        const int ii = on ? i : 0;
+        const double nxt = xs[ii];
+        if (on) prop[(int64_t)c * d + i] = nxt;
+        const int n = (d - p * 64 < 64) ? d - p * 64 : 64;
+        if (!dir) {
+            lp = wave_seq_sum_from(lp, n, on ? prior::log_pdf(kind[ii], p0[ii], p1[ii], p2[ii], nxt) : 0.0);
+        } else {
+            const bool uni = on && kind[ii] != BCM3HIP_PRIOR_DIRICHLET;
+            const double ul = uni ? prior::log_pdf(kind[ii], p0[ii], p1[ii], p2[ii], nxt) : 0.0;
+            const uint64_t um = __builtin_amdgcn_ballot_w64(uni);
+            for (int j = 0; j < n; j++)
+                if ((um >> j) & 1) lp += lane_bcast(ul, j);
+        }
+    }
+    if (lane == 0) {
+        lprior_prop[c] = lp;
+        log_mh[c] = lmh;
+    }
+}
+
 // accept_one for a blocked move: the component that proposed and its acceptance EMA are the block's
 // (sel_p, ema_row)
 __device__ __forceinline__ bool accept_block_one(int c, int d, const double* __restrict__ temps, const double* __restrict__ prop,
@@ -1645,7 +1881,7 @@ int bcm3hip_ptmh_accept_adaptive(int C, int d, const double* temps, const double
 // blocked moves read kind, kmax, t_dof, the scaling constants and the bounds of the proposal struct
 static bool blocked_ok(const bcm3hip_proposal* P, const bcm3hip_blocks* B, int C, int d, int submove)
 {
-    if (!P || !B || d > 64 || submove < 0 || submove >= d) return false;
+    if (!P || !B || d > BCM3HIP_BLOCKED_MAX_D || submove < 0 || submove >= d) return false;
     if (P->kind != BCM3HIP_PROPOSAL_GLOBAL_COVARIANCE && P->kind != BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) return false;
     if (P->kmax < 1 || P->kmax > BCM3HIP_PROPOSAL_KMAX) return false;
     if (C > 0 && (!P->lower || !P->upper || !B->nblocks || !B->block_offset || !B->block_vars || !B->target ||
@@ -1666,9 +1902,15 @@ int bcm3hip_ptmh_propose_blocked(int C, int d, int submove, const int32_t* prior
                    !lprior_prop || !log_mh)))
         return BCM3HIP_ERR_ARG;
     if (C == 0) return 0;
-    hipLaunchKernelGGL(ptmh_propose_blocked_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, C, d, submove,
-                       prior_kind, prior_p0, prior_p1, prior_p2, temps, values, prop, lprior_prop, log_mh, *proposal,
-                       *blocks, chain0, seed, iter);
+    // the full vector on one wavefront's lanes up to 64 variables, beyond in passes through LDS
+    if (d <= 64)
+        hipLaunchKernelGGL(ptmh_propose_blocked_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, C, d, submove,
+                           prior_kind, prior_p0, prior_p1, prior_p2, temps, values, prop, lprior_prop, log_mh,
+                           *proposal, *blocks, chain0, seed, iter);
+    else
+        hipLaunchKernelGGL(ptmh_propose_blocked_wide_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, C, d, submove,
+                           prior_kind, prior_p0, prior_p1, prior_p2, temps, values, prop, lprior_prop, log_mh,
+                           *proposal, *blocks, chain0, seed, iter);
     return hipGetLastError() == hipSuccess ? 0 : BCM3HIP_ERR_HIP;
 }
 

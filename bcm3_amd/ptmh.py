@@ -20,6 +20,8 @@ from .likelihood import Likelihood, lib as host_lib
 PROPOSALS = {"global_covariance": 0, "gaussian_mixture": 1, "gaussian_mixture_adjustedAIC": 2, "random_walk": 3}
 SCHEMES = {"deterministic_even_odd": 0, "stochastic_even_odd": 1, "stochastic_random": 2}
 BLOCKINGS = {"one_block": 0, "no_blocking": 1, "explicit": 2}
+# limits of the blocked moves (include/bcm3hip.h: BCM3HIP_BLOCKED_MAX_D, BCM3HIP_BLOCK_MAX_SIZE)
+BLOCKED_MAX_D, BLOCK_MAX_SIZE = 1024, 64
 TRANSPORT_NONE, TRANSPORT_RCCL, TRANSPORT_LOCAL, TRANSPORT_SOCKET = 0, 1, 2, 3
 COUNTERS = ("attempted_mutate", "accepted_mutate", "attempted_exchange", "accepted_exchange", "samples_done",
             "adaptations_done", "iterations", "rounds", "likelihood_launches", "evaluated_entries")
@@ -169,7 +171,9 @@ class PTMHNative:
                  blocks=None, **options):
         """blocking: "one_block" (default), "no_blocking" (one variable per block) or "explicit" with
         blocks = the block id of every variable (0..B-1, each used; giving blocks alone implies
-        "explicit"). With blocks a mutate move is one sub-move per block and `speculate` is ignored."""
+        "explicit"). With blocks a mutate move is one sub-move per block and `speculate` is ignored;
+        at most 1024 variables, blocks of at most 64 (a single explicit block of more than 64 variables
+        is refused at create: "one_block" is the way to get that)."""
         _hip.lib()
         L = _lib()
         cfg = PTMHConfig()

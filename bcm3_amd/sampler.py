@@ -231,7 +231,8 @@ class PTMHDevice:
         """blocking / blocks: the variable blocks of the mutate move as bcm3_amd.ptmh.PTMHNative takes
         them ("one_block", "no_blocking", or "explicit" with one block id per variable): one sub-move
         per block -- propose_blocked, the likelihood launch, accept_blocked -- then one history add
-        (SamplerPTChain.cpp:249-309), proposals adapted per block."""
+        (SamplerPTChain.cpp:249-309), proposals adapted per block. At most 1024 variables, blocks of
+        at most 64: a larger block raises ValueError, "one_block" is the way to get that."""
         from . import _hip
         self._hip = _hip
         _hip.lib()  # fails loudly without the HIP library
@@ -299,11 +300,16 @@ class PTMHDevice:
             blocking = "explicit"
         self.blocked = None
         if blocking != "one_block":
-            if not self.adaptive or d > 64:
-                raise ValueError("variable blocks need an adaptive proposal and at most 64 variables")
-            from .ptmh import build_blocks
+            from .ptmh import BLOCK_MAX_SIZE, BLOCKED_MAX_D, build_blocks
             from .proposal import BlockedProposal
-            self.blocked = BlockedProposal(self.proposal, *build_blocks(blocking, d, blocks))
+            if not self.adaptive or d > BLOCKED_MAX_D:
+                raise ValueError(f"variable blocks need an adaptive proposal and at most {BLOCKED_MAX_D} variables ({d})")
+            nb, off, var = build_blocks(blocking, d, blocks)
+            for b in range(nb):  # a block is one wavefront of the propose kernels
+                if off[b + 1] - off[b] > BLOCK_MAX_SIZE:
+                    raise ValueError(f"block {b} has {off[b + 1] - off[b]} variables; a block holds at most "
+                                     f"{BLOCK_MAX_SIZE} (one_block moves all variables at once)")
+            self.blocked = BlockedProposal(self.proposal, nb, off, var)
             self._cold = int((self.T == 0.0).sum().item())  # T == 0 chains: prior draws in sub-move 0 only
         self._initial_positions(initial_position_tries)
 

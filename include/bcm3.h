@@ -194,7 +194,9 @@ typedef struct {
                                     BCM3_PTMH_NO_BLOCKING or BCM3_PTMH_EXPLICIT_BLOCKS. With blocks, a
                                     mutate move is one sub-move per block (its own proposal, likelihood
                                     launch, accept and scale adaptation; SamplerPTChain.cpp:249-307);
-                                    adaptive proposals and at most 64 variables; `speculate` is ignored */
+                                    adaptive proposals, at most 1024 variables, blocks of at most 64
+                                    (a single explicit block of more than 64 variables is refused:
+                                    BCM3_PTMH_ONE_BLOCK is the way to get that); `speculate` is ignored */
     const int32_t* block_of_variable; /* BCM3_PTMH_EXPLICIT_BLOCKS: the block of each of the d variables
                                     (bcm3_build_blocks); read by bcm3_ptmh_create only */
 } bcm3_ptmh_config;

@@ -618,7 +618,17 @@ int bcm3hip_ptmh_accept_adaptive(int C, int d, const double* temps, const double
  *   mean of component k mean[c * kmax * d + kmax * o + k * s + i]           (i < s)
  *   factor of k         chol[c * kmax * d * d + kmax * o * d + k * s * s + i * s + j]
  * so one block of all d variables in order has the mean / chol layout of bcm3hip_proposal.
- * d <= 64. All pointers are device pointers. */
+ * At most BCM3HIP_BLOCKED_MAX_D (1024) variables, blocks of at most 64 (BCM3HIP_BLOCK_MAX_SIZE): up
+ * to 64 variables the full vector lies on one wavefront's lanes, beyond it is handled in passes of
+ * 64 through LDS (ptmh_propose_blocked_wide_kernel); a block is always one wavefront. A single
+ * explicit block of more than 64 variables is refused -- one_block (bcm3hip_ptmh_propose_adaptive)
+ * is the way to move all variables at once.
+ * Size: mean is C * kmax * d doubles and chol C * kmax * d * d doubles (8 C kmax d^2 bytes: 0.51 GB
+ * at C = 256, kmax = 13, d = 138) whatever the partition -- the packed blocks use
+ * kmax * sum_b s_b^2 of each chain's kmax * d * d -- and the host adaptation moves both buffers
+ * over the bus in each direction. All pointers are device pointers. */
+#define BCM3HIP_BLOCKED_MAX_D 1024
+#define BCM3HIP_BLOCK_MAX_SIZE 64
 typedef struct {
     const int32_t* nblocks;      /* [C] */
     const int32_t* block_offset; /* [C][d + 1] */
@@ -644,7 +654,10 @@ typedef struct {
  * scaling constants and the bounds (its per-chain state is not read). The counter RNG's key gains
  * the sub-move (seed + submove * 0x9E3779B97F4A7C15, normal slot = position in the block): with one
  * block of all d variables in order, prop / lprior_prop / log_mh and the state updates are those of
- * bcm3hip_ptmh_propose_adaptive bit for bit. */
+ * bcm3hip_ptmh_propose_adaptive bit for bit. A block's proposal does not depend on the variables
+ * outside it: at d > 64 its new coordinates, log_mh and selected component are those of the same
+ * block in a problem of its variables alone. d > BCM3HIP_BLOCKED_MAX_D is an argument error (both
+ * calls); the caller validates the block sizes (a table entry above 64 is clamped, never trusted). */
 int bcm3hip_ptmh_propose_blocked(int C, int d, int submove, const int32_t* prior_kind, const double* prior_p0,
                                  const double* prior_p1, const double* prior_p2, const double* temps,
                                  const double* values, double* prop, double* lprior_prop, double* log_mh,
