@@ -444,6 +444,220 @@ __global__ void __launch_bounds__(64) gmm_eval_wave_kernel(int n, int d, int K, 
     if (logpdf && lane == 0) logpdf[p] = lsum;
 }
 
+// ---- one wavefront per chain: the pieces the propose kernels share ----
+
+// The T = 0 prior draw of the full vector, lane i = variable i (RNG slot = variable)
+__device__ __forceinline__ double wave_prior_draw(int d, const int32_t* __restrict__ kind,
+                                                  const double* __restrict__ p0, const double* __restrict__ p1,
+                                                  const double* __restrict__ p2, bool dir, uint64_t seed,
+                                                  uint64_t iter, uint64_t gc)
+{
+    const int lane = threadIdx.x & 63;
+    const int li = (lane < d) ? lane : 0;
+    double nxt = prior::sample(kind[li], p0[li], p1[li], p2[li], seed, iter, gc, li);
+    if (dir) {
+        // MultivariateMarginal::Sample: each member's Gamma draw over the group's sum
+        for (int f = 0; f < d; f++) {
+            if (kind[f] != BCM3HIP_PRIOR_DIRICHLET || (int)p1[f] != f) continue;
+            const int l = prior::dirichlet_last(d, kind, p1, f);
+            double sum = 0.0;
+            for (int j = f; j <= l; j++) sum += lane_bcast(nxt, j);
+            const double inv = 1.0 / sum;
+            if (lane >= f && lane <= l) nxt *= inv;
+        }
+    }
+    return nxt;
+}
+
+// Dirichlet residual after the MH ratio of the unmodified proposal (SamplerPTChain.cpp:270-278):
+// the last member of every group of the full vector nxt (lane i = variable i) becomes 1 - the others
+__device__ __forceinline__ double wave_dirichlet_residual(int d, const int32_t* __restrict__ kind,
+                                                          const double* __restrict__ p1, double nxt)
+{
+    const int lane = threadIdx.x & 63;
+    for (int f = 0; f < d; f++) {
+        if (kind[f] != BCM3HIP_PRIOR_DIRICHLET || (int)p1[f] != f) continue;
+        const int l = prior::dirichlet_last(d, kind, p1, f);
+        double sum = 0.0;
+        for (int j = f; j < l; j++) sum += lane_bcast(nxt, j);
+        if (lane == l) nxt = 1.0 - sum;
+    }
+    return nxt;
+}
+
+// log prior of the full vector nxt (lane i = variable i), uniform result
+__device__ __forceinline__ double wave_log_prior(int d, const int32_t* __restrict__ kind,
+                                                 const double* __restrict__ p0, const double* __restrict__ p1,
+                                                 const double* __restrict__ p2, bool dir, double nxt)
+{
+    const int lane = threadIdx.x & 63;
+    const bool on = lane < d;
+    const int li = on ? lane : 0;
+    if (!dir) return wave_seq_sum(d, on ? prior::log_pdf(kind[li], p0[li], p1[li], p2[li], nxt) : 0.0);
+    // PriorIndependence::EvaluateLogPDF: multivariate groups first, then the univariate
+    // marginals in variable order
+    const double ul = (on && kind[li] != BCM3HIP_PRIOR_DIRICHLET) ? prior::log_pdf(kind[li], p0[li], p1[li], p2[li], nxt)
+                                                                    : 0.0;
+    double lp = 0.0;
+    for (int f = 0; f < d; f++)
+        if (kind[f] == BCM3HIP_PRIOR_DIRICHLET && (int)p1[f] == f)
+            lp += prior::dirichlet_log_pdf(f, prior::dirichlet_last(d, kind, p1, f), p0, p2[f],
+                                           [&](int j) { return lane_bcast(nxt, j); });
+    for (int i = 0; i < d; i++)
+        if (kind[i] != BCM3HIP_PRIOR_DIRICHLET) lp += lane_bcast(ul, i);
+    return lp;
+}
+
+// The proposal state a block draw works on: a chain's (bcm3hip_proposal) or a (chain, block)'s
+// (bcm3hip_blocks), mean and chol packed in the draw's dimension
+struct block_state {
+    const int32_t* ncomp;
+    const int32_t* selected;
+    double* scale;  // [kmax]
+    const double* ema;
+    const double* logc;
+    const double* weights;
+    const double* mean;  // [kmax][n]
+    const double* chol;  // [kmax][n][n]
+    double target;
+};
+
+// what a block draw leaves in lane j: x = the new coordinate j; uniform: log_mh, the selected
+// component, and the scale Update changed (component upd, -1 for none, and its new value sc)
+struct block_draw {
+    double x, log_mh, sc;
+    int sel, upd;
+};
+
+// One draw from an adaptive proposal in n <= 64 dimensions, lane j = coordinate j: Proposal::Update's
+// scale step, the component selection, the Cholesky draw with the t scale, the reflection on
+// (*lo, *hi) and the mixture's MH ratio. cur: this lane's coordinate of the point proposed from;
+// lo, hi: this lane's bounds, read where they are used (read before the draw they cost the narrow
+// blocked kernel 2 % of a launch).
+// The one definition of this arithmetic: propose_wave_one runs it in d with the chain's state,
+// the blocked kernels in the block's size with the (chain, block)'s. SPEC = false: the new scale is
+// stored (lane 0), where Update stores it. SPEC = true: nothing is stored, and the acceptance EMA of
+// the component Update reads is ema_last.
+template <bool SPEC>
+__device__ __forceinline__ block_draw wave_block_draw(int n, double cur, const double* lo, const double* hi,
+                                                      const bcm3hip_proposal& P, const block_state& st,
+                                                      double ema_last, uint64_t seed, uint64_t iter, uint64_t gc)
+{
+    const int lane = threadIdx.x & 63;
+    const bool on = lane < n;
+    const int li = on ? lane : 0;
+    const auto& [ncomp, selected, scale, ema, logc, w, mean, chol, target] = st;
+    const int Km = P.kmax;
+    int K = (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) ? *ncomp : 1;
+    K = (K < 1) ? 1 : ((K > Km) ? Km : K);
+    const double slr = P.scaling_learning_rate;
+    int sel;
+    double rf = 0.0;
+    // the scale Update changes (component upd, new value sc): kept in registers, since other
+    // lanes read it after lane 0's store
+    int upd = -1;
+    double sc = 0.0;
+    if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
+        const int last = *selected;
+        if (last != -1) {
+            const double lrate = 1.0 + u01(rng_key(seed, iter, gc, rng::KEY_UPDATE)) * slr * K;
+            sc = scale[last];
+            const double e = SPEC ? ema_last : ema[last];
+            if (e < target / (1.0 - slr)) {
+                sc /= lrate;
+                sc = (sc > 1e-4) ? sc : 1e-4;
+            } else if (e > (1 + slr) * target) {
+                sc *= lrate;
+                sc = (sc < 10.0) ? sc : 10.0;
+            }
+            if (!SPEC && lane == 0) scale[last] = sc;
+            upd = last;
+        }
+        rf = wave_responsibilities(K, n, cur, mean, chol, logc, w, lane);
+        const double u = u01(rng_key(seed, iter, gc, rng::KEY_SELECT));
+        double acc = 0.0;
+        sel = K - 1;
+        for (int k = 0; k < K; k++) {
+            acc += lane_bcast(rf, k);
+            if (u < acc) {
+                sel = k;
+                break;
+            }
+        }
+    } else {
+        const double lrate = 1.0 + u01(rng_key(seed, iter, gc, rng::KEY_UPDATE)) * slr;
+        sc = scale[0];
+        const double e = SPEC ? ema_last : ema[0];
+        if (e < 0.952381 * target) {
+            sc /= lrate;
+            sc = (sc > 1e-4) ? sc : 1e-4;
+        } else if (e > 1.05 * target) {
+            sc *= lrate;
+            sc = (sc < 10.0) ? sc : 10.0;
+        }
+        if (!SPEC && lane == 0) scale[0] = sc;
+        upd = 0;
+        sel = 0;
+    }
+    double t_scale = 1.0;
+    if (P.t_dof > 0.0) {
+        const double wg = gamma_draw(0.5 * P.t_dof, 0.5 * P.t_dof, seed, iter, gc);
+        t_scale = 1.0 / sqrt(wg);
+    }
+    const double* Ls = chol + (int64_t)sel * n * n + (int64_t)li * n;
+    const double z = normal01(seed, iter, gc, li);
+    const double f = t_scale * ((sel == upd) ? sc : scale[sel]);
+    double x = 0.0;
+    for (int j = 0; j < n; j++) {
+        const double zj = lane_bcast(z, j);
+        const double a = x + Ls[j] * zj;  // Ls: this lane's row (row 0 for lanes >= n)
+        x = (j <= lane) ? a : x;
+    }
+    const double nxt = reflect(x * f + cur, *lo, *hi);
+    double lmh = 0.0;
+    if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE && n <= 16) {
+        // the reverse responsibilities at nxt and the MH solve of component k use the same
+        // L_k: one pass solves both (values as in the branch below, bit for bit)
+        double r = 0.0, qv = 0.0;
+        for (int k = 0; k < K; k++) {
+            const double sk = (k == upd) ? sc : scale[k];
+            const double ta0 = on ? nxt - mean[k * n + lane] : 0.0;
+            const double tb0 = on ? (nxt - cur) / sk : 0.0;
+            double ta, tb;
+            wave_lower_solve2_reg<16>(n, chol + (int64_t)k * n * n + (int64_t)li * n, ta0, tb0, lane, ta, tb);
+            const double rk = (logc[k] - 0.5 * wave_seq_sum(n, on ? ta * ta : 0.0)) + log(w[k]);
+            r = (lane == k) ? rk : r;
+            const double q = 0.5 * wave_seq_sum(n, on ? tb * tb : 0.0);
+            qv = (lane == k) ? q : qv;
+        }
+        double lsum;
+        const double rr = wave_normalize_resp(K, r, lsum);
+        double fwd = -INFINITY, rev = -INFINITY;
+        for (int k = 0; k < K; k++) {
+            const double sk = (k == upd) ? sc : scale[k];
+            const double base = -log(sk * sk) + logc[k];
+            const double q = lane_bcast(qv, k);
+            fwd = logsum2(fwd, (base - q) + log(lane_bcast(rf, k)));
+            rev = logsum2(rev, (base - q) + log(lane_bcast(rr, k)));
+        }
+        lmh = rev - fwd;
+    } else if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
+        const double rr = wave_responsibilities(K, n, nxt, mean, chol, logc, w, lane);
+        double fwd = -INFINITY, rev = -INFINITY;
+        for (int k = 0; k < K; k++) {
+            const double sk = (k == upd) ? sc : scale[k];
+            const double t0 = on ? (nxt - cur) / sk : 0.0;
+            const double t = wave_lower_solve(n, chol + (int64_t)k * n * n + (int64_t)li * n, t0, lane);
+            const double base = -log(sk * sk) + logc[k];
+            const double q = 0.5 * wave_seq_sum(n, on ? t * t : 0.0);
+            fwd = logsum2(fwd, (base - q) + log(lane_bcast(rf, k)));
+            rev = logsum2(rev, (base - q) + log(lane_bcast(rr, k)));
+        }
+        lmh = rev - fwd;
+    }
+    return {nxt, lmh, sc, sel, upd};
+}
+
 // One chain's proposal (see ptmh_propose_wave_kernel). cur_row: the point proposed from. SPEC = false:
 // the proposal state is updated in place (Proposal::Update's scale, the selected component), the
 // results go to out_row / *lprior_out / *log_mh_out. SPEC = true (speculative candidates for the next
@@ -469,170 +683,28 @@ __device__ __forceinline__ void propose_wave_one(int c, int d, const int32_t* __
     double lmh = 0.0;
     const bool dir = prior::has_dirichlet(d, kind);
     if (temps[c] == 0.0) {
-        nxt = prior::sample(kind[li], p0[li], p1[li], p2[li], seed, iter, gc, li);
-        if (dir) {
-            // MultivariateMarginal::Sample: each member's Gamma draw over the group's sum
-            for (int f = 0; f < d; f++) {
-                if (kind[f] != BCM3HIP_PRIOR_DIRICHLET || (int)p1[f] != f) continue;
-                const int l = prior::dirichlet_last(d, kind, p1, f);
-                double sum = 0.0;
-                for (int j = f; j <= l; j++) sum += lane_bcast(nxt, j);
-                const double inv = 1.0 / sum;
-                if (lane >= f && lane <= l) nxt *= inv;
-            }
-        }
+        nxt = wave_prior_draw(d, kind, p0, p1, p2, dir, seed, iter, gc);
     } else {
-        const int Km = P.kmax;
-        int K = (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) ? P.ncomp[c] : 1;
-        K = (K < 1) ? 1 : ((K > Km) ? Km : K);
-        double* scale = P.scale + (int64_t)c * Km;
-        double* ema = P.ema + (int64_t)c * Km;
-        const double* mean = P.mean + (int64_t)c * Km * d;
-        const double* chol = P.chol + (int64_t)c * Km * d * d;
-        const double* logc = P.logc + (int64_t)c * Km;
-        const double* w = P.weights + (int64_t)c * Km;
-        const double slr = P.scaling_learning_rate;
-        const double target = P.target_acceptance;
-        int sel;
-        double rf = 0.0;
-        // the scale Update changes (component upd, new value sc): kept in registers, since other
-        // lanes read it after lane 0's store
-        int upd = -1;
-        double sc = 0.0;
-        if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
-            const int last = P.selected[c];
-            if (last != -1) {
-                const double lrate = 1.0 + u01(rng_key(seed, iter, gc, rng::KEY_UPDATE)) * slr * K;
-                sc = scale[last];
-                const double e = SPEC ? ema_last : ema[last];
-                if (e < target / (1.0 - slr)) {
-                    sc /= lrate;
-                    sc = (sc > 1e-4) ? sc : 1e-4;
-                } else if (e > (1 + slr) * target) {
-                    sc *= lrate;
-                    sc = (sc < 10.0) ? sc : 10.0;
-                }
-                if (!SPEC && lane == 0) scale[last] = sc;
-                upd = last;
-            }
-            rf = wave_responsibilities(K, d, cur, mean, chol, logc, w, lane);
-            const double u = u01(rng_key(seed, iter, gc, rng::KEY_SELECT));
-            double acc = 0.0;
-            sel = K - 1;
-            for (int k = 0; k < K; k++) {
-                acc += lane_bcast(rf, k);
-                if (u < acc) {
-                    sel = k;
-                    break;
-                }
-            }
-        } else {
-            const double lrate = 1.0 + u01(rng_key(seed, iter, gc, rng::KEY_UPDATE)) * slr;
-            sc = scale[0];
-            const double e = SPEC ? ema_last : ema[0];
-            if (e < 0.952381 * target) {
-                sc /= lrate;
-                sc = (sc > 1e-4) ? sc : 1e-4;
-            } else if (e > 1.05 * target) {
-                sc *= lrate;
-                sc = (sc < 10.0) ? sc : 10.0;
-            }
-            if (!SPEC && lane == 0) scale[0] = sc;
-            upd = 0;
-            sel = 0;
-        }
-        double t_scale = 1.0;
-        if (P.t_dof > 0.0) {
-            const double wg = gamma_draw(0.5 * P.t_dof, 0.5 * P.t_dof, seed, iter, gc);
-            t_scale = 1.0 / sqrt(wg);
-        }
-        const double* Ls = chol + (int64_t)sel * d * d + (int64_t)li * d;
-        const double z = normal01(seed, iter, gc, li);
-        const double f = t_scale * ((sel == upd) ? sc : scale[sel]);
-        double x = 0.0;
-        for (int j = 0; j < d; j++) {
-            const double zj = lane_bcast(z, j);
-            const double a = x + Ls[j] * zj;  // Ls: this lane's row (row 0 for lanes >= d)
-            x = (j <= lane) ? a : x;
-        }
-        nxt = reflect(x * f + cur, P.lower[li], P.upper[li]);
-        if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE && d <= 16) {
-            // the reverse responsibilities at nxt and the MH solve of component k use the same
-            // L_k: one pass solves both (values as in the branch below, bit for bit)
-            double r = 0.0, qv = 0.0;
-            for (int k = 0; k < K; k++) {
-                const double sk = (k == upd) ? sc : scale[k];
-                const double ta0 = on ? nxt - mean[k * d + lane] : 0.0;
-                const double tb0 = on ? (nxt - cur) / sk : 0.0;
-                double ta, tb;
-                wave_lower_solve2_reg<16>(d, chol + (int64_t)k * d * d + (int64_t)li * d, ta0, tb0, lane, ta, tb);
-                const double rk = (logc[k] - 0.5 * wave_seq_sum(d, on ? ta * ta : 0.0)) + log(w[k]);
-                r = (lane == k) ? rk : r;
-                const double q = 0.5 * wave_seq_sum(d, on ? tb * tb : 0.0);
-                qv = (lane == k) ? q : qv;
-            }
-            double lsum;
-            const double rr = wave_normalize_resp(K, r, lsum);
-            double fwd = -INFINITY, rev = -INFINITY;
-            for (int k = 0; k < K; k++) {
-                const double sk = (k == upd) ? sc : scale[k];
-                const double base = -log(sk * sk) + logc[k];
-                const double q = lane_bcast(qv, k);
-                fwd = logsum2(fwd, (base - q) + log(lane_bcast(rf, k)));
-                rev = logsum2(rev, (base - q) + log(lane_bcast(rr, k)));
-            }
-            lmh = rev - fwd;
-        } else if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
-            const double rr = wave_responsibilities(K, d, nxt, mean, chol, logc, w, lane);
-            double fwd = -INFINITY, rev = -INFINITY;
-            for (int k = 0; k < K; k++) {
-                const double sk = (k == upd) ? sc : scale[k];
-                const double t0 = on ? (nxt - cur) / sk : 0.0;
-                const double t = wave_lower_solve(d, chol + (int64_t)k * d * d + (int64_t)li * d, t0, lane);
-                const double base = -log(sk * sk) + logc[k];
-                const double q = 0.5 * wave_seq_sum(d, on ? t * t : 0.0);
-                fwd = logsum2(fwd, (base - q) + log(lane_bcast(rf, k)));
-                rev = logsum2(rev, (base - q) + log(lane_bcast(rr, k)));
-            }
-            lmh = rev - fwd;
-        }
-        if (dir) {
-            // Dirichlet residual after the MH ratio of the unmodified proposal (SamplerPTChain.cpp:270-278)
-            for (int f = 0; f < d; f++) {
-                if (kind[f] != BCM3HIP_PRIOR_DIRICHLET || (int)p1[f] != f) continue;
-                const int l = prior::dirichlet_last(d, kind, p1, f);
-                double sum = 0.0;
-                for (int j = f; j < l; j++) sum += lane_bcast(nxt, j);
-                if (lane == l) nxt = 1.0 - sum;
-            }
-        }
+        const int64_t ck = (int64_t)c * P.kmax;
+        const block_state st = {P.ncomp + c,    P.selected + c,  P.scale + ck,        P.ema + ck,         P.logc + ck,
+                                P.weights + ck, P.mean + ck * d, P.chol + ck * d * d, P.target_acceptance};
+        const block_draw b =
+            wave_block_draw<SPEC>(d, cur, P.lower + li, P.upper + li, P, st, ema_last, seed, iter, gc);
+        nxt = b.x;
+        lmh = b.log_mh;
+        if (dir) nxt = wave_dirichlet_residual(d, kind, p1, nxt);
         if (SPEC) {
             if (lane == 0) {
-                *sel_out = sel;
-                *upd_out = upd;
-                *sc_out = sc;
+                *sel_out = b.sel;
+                *upd_out = b.upd;
+                *sc_out = b.sc;
             }
         } else if (lane == 0) {
-            P.selected[c] = sel;
+            P.selected[c] = b.sel;
         }
     }
     if (on) out_row[lane] = nxt;
-    double lp;
-    if (!dir) {
-        lp = wave_seq_sum(d, on ? prior::log_pdf(kind[li], p0[li], p1[li], p2[li], nxt) : 0.0);
-    } else {
-        // PriorIndependence::EvaluateLogPDF: multivariate groups first, then the univariate
-        // marginals in variable order
-        const double ul = (on && kind[li] != BCM3HIP_PRIOR_DIRICHLET) ? prior::log_pdf(kind[li], p0[li], p1[li], p2[li], nxt)
-                                                                        : 0.0;
-        lp = 0.0;
-        for (int f = 0; f < d; f++)
-            if (kind[f] == BCM3HIP_PRIOR_DIRICHLET && (int)p1[f] == f)
-                lp += prior::dirichlet_log_pdf(f, prior::dirichlet_last(d, kind, p1, f), p0, p2[f],
-                                               [&](int j) { return lane_bcast(nxt, j); });
-        for (int i = 0; i < d; i++)
-            if (kind[i] != BCM3HIP_PRIOR_DIRICHLET) lp += lane_bcast(ul, i);
-    }
+    const double lp = wave_log_prior(d, kind, p0, p1, p2, dir, nxt);
     if (lane == 0) {
         *lprior_out = lp;
         *log_mh_out = lmh;
@@ -667,14 +739,16 @@ __global__ void __launch_bounds__(64) ptmh_propose_adaptive_kernel(
                   iter, work + 2 * Km, work + 2 * Km + d, work, work + Km);
 }
 
-// Sampler::TestSample / MutateMove's accept of chain c (one thread per chain); returns the flag
+// Sampler::TestSample / MutateMove's accept of chain c (one thread per chain); returns the flag.
+// sel_p, ema_row: the component that proposed and the acceptance EMAs of its proposal, the chain's
+// (P.selected + c, P.ema + c * P.kmax) or, for a blocked move, the block's
 __device__ __forceinline__ bool accept_one(int c, int d, const double* __restrict__ temps, const double* __restrict__ prop,
                            const double* __restrict__ lprior_prop, const double* __restrict__ llh_prop,
                            const double* __restrict__ log_mh, double learning_rate, double* __restrict__ values,
                            double* __restrict__ lprior, double* __restrict__ llh, double* __restrict__ lpp,
                            uint8_t* __restrict__ acc_out, unsigned long long* __restrict__ accepted,
-                           int32_t* __restrict__ nan_llh, const bcm3hip_proposal& P, int64_t chain0, uint64_t seed,
-                           uint64_t iter)
+                           int32_t* __restrict__ nan_llh, const int32_t* sel_p, double* ema_row, double ema_period,
+                           int64_t chain0, uint64_t seed, uint64_t iter)
 {
     const double T = temps[c];
     const double nl = llh_prop[c] * learning_rate;  // Sampler::EvaluateLikelihood
@@ -700,9 +774,9 @@ __device__ __forceinline__ bool accept_one(int c, int d, const double* __restric
             acc = u01(rng_key(seed, iter, (uint64_t)(chain0 + c), rng::KEY_ACCEPT)) < tp;
         }
         // NotifyAccepted (EMA of the acceptance of the component that proposed)
-        const int sel = P.selected[c];
-        double* ema = P.ema + (int64_t)c * P.kmax + sel;
-        const double alpha = 2.0 / (P.scaling_ema_period + 1);
+        const int sel = *sel_p;
+        double* ema = ema_row + sel;
+        const double alpha = 2.0 / (ema_period + 1);
         *ema += ((acc ? 1.0 : 0.0) - *ema) * alpha;
     }
     if (acc) {
@@ -729,7 +803,7 @@ __global__ void ptmh_accept_adaptive_kernel(int C, int d, const double* __restri
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     accept_one(c, d, temps, prop, lprior_prop, llh_prop, log_mh, learning_rate, values, lprior, llh, lpp, acc_out,
-               accepted, nan_llh, P, chain0, seed, iter);
+               accepted, nan_llh, P.selected + c, P.ema + (int64_t)c * P.kmax, P.scaling_ema_period, chain0, seed, iter);
 }
 
 // ---- blocked moves (include/bcm3hip.h "blocked Metropolis-within-Gibbs moves") ----
@@ -742,11 +816,27 @@ __device__ __forceinline__ uint64_t submove_seed(uint64_t seed, int m)
 
 __device__ __forceinline__ int lane_bcast_i(int x, int j) { return __builtin_amdgcn_readlane(x, j); }
 
+// the proposal state of chain c's block m, whose variables start at offset o of the chain's table
+__device__ __forceinline__ block_state blocked_state(const bcm3hip_proposal& P, const bcm3hip_blocks& B, int c, int d,
+                                                     int m, int o)
+{
+    const int Km = P.kmax;
+    const int64_t cb = (int64_t)c * d + m;
+    return {B.ncomp + cb,
+            B.selected + cb,
+            B.scale + cb * Km,
+            B.ema + cb * Km,
+            B.logc + cb * Km,
+            B.weights + cb * Km,
+            B.mean + (int64_t)c * Km * d + (int64_t)Km * o,
+            B.chol + (int64_t)c * Km * d * d + (int64_t)Km * o * d,
+            B.target[cb]};
+}
+
 // One wavefront per chain. Two index spaces: the full vector has lane i = variable i (copy, Dirichlet
-// residual, prior), the block's proposal has lane j = position j in the block (s = its size), with
-// the arithmetic of propose_wave_one in the block's dimensions -- its helpers are called with
-// d := s and the block's packed mean / factors -- so one block of all variables in order repeats
-// propose_wave_one operation for operation.
+// residual, prior), the block's proposal has lane j = position j in the block (s = its size):
+// wave_block_draw, which propose_wave_one runs in d, here in s on the block's packed mean / factors,
+// so one block of all variables in order repeats propose_wave_one operation for operation.
 __global__ void __launch_bounds__(64) ptmh_propose_blocked_kernel(
     int C, int d, int m, const int32_t* __restrict__ kind, const double* __restrict__ p0, const double* __restrict__ p1,
     const double* __restrict__ p2, const double* __restrict__ temps, const double* __restrict__ values,
@@ -770,17 +860,7 @@ __global__ void __launch_bounds__(64) ptmh_propose_blocked_kernel(
     const bool active = (T == 0.0) ? (m == 0) : (m < nb);
     if (lane == 0) B.active[c] = active ? 1 : 0;
     if (active && T == 0.0) {
-        nxt = prior::sample(kind[li], p0[li], p1[li], p2[li], seed, iter, gc, li);
-        if (dir) {
-            for (int f = 0; f < d; f++) {
-                if (kind[f] != BCM3HIP_PRIOR_DIRICHLET || (int)p1[f] != f) continue;
-                const int l = prior::dirichlet_last(d, kind, p1, f);
-                double sum = 0.0;
-                for (int j = f; j <= l; j++) sum += lane_bcast(nxt, j);
-                const double inv = 1.0 / sum;
-                if (lane >= f && lane <= l) nxt *= inv;
-            }
-        }
+        nxt = wave_prior_draw(d, kind, p0, p1, p2, dir, seed, iter, gc);
     } else if (active) {
         // the block: offset o, size s (clamped into the table, so a malformed table cannot index
         // outside the chain's rows)
@@ -793,151 +873,21 @@ __global__ void __launch_bounds__(64) ptmh_propose_blocked_kernel(
         int var = B.block_vars[(int64_t)c * d + o + lb];
         var = (var < 0) ? 0 : ((var > d - 1) ? d - 1 : var);
         const double curb = values[(int64_t)c * d + var];
-        const int Km = P.kmax;
-        const int64_t cb = (int64_t)c * d + m;
-        int K = (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) ? B.ncomp[cb] : 1;
-        K = (K < 1) ? 1 : ((K > Km) ? Km : K);
-        double* scale = B.scale + cb * Km;
-        const double* ema = B.ema + cb * Km;
-        const double* logc = B.logc + cb * Km;
-        const double* w = B.weights + cb * Km;
-        const double* mean = B.mean + (int64_t)c * Km * d + (int64_t)Km * o;
-        const double* chol = B.chol + (int64_t)c * Km * d * d + (int64_t)Km * o * d;
-        const double slr = P.scaling_learning_rate;
-        const double target = B.target[cb];
-        int sel;
-        double rf = 0.0;
-        int upd = -1;
-        double sc = 0.0;
-        if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
-            const int last = B.selected[cb];
-            if (last != -1) {
-                const double lrate = 1.0 + u01(rng_key(seed, iter, gc, rng::KEY_UPDATE)) * slr * K;
-                sc = scale[last];
-                const double e = ema[last];
-                if (e < target / (1.0 - slr)) {
-                    sc /= lrate;
-                    sc = (sc > 1e-4) ? sc : 1e-4;
-                } else if (e > (1 + slr) * target) {
-                    sc *= lrate;
-                    sc = (sc < 10.0) ? sc : 10.0;
-                }
-                if (lane == 0) scale[last] = sc;
-                upd = last;
-            }
-            rf = wave_responsibilities(K, s, curb, mean, chol, logc, w, lane);
-            const double u = u01(rng_key(seed, iter, gc, rng::KEY_SELECT));
-            double acc = 0.0;
-            sel = K - 1;
-            for (int k = 0; k < K; k++) {
-                acc += lane_bcast(rf, k);
-                if (u < acc) {
-                    sel = k;
-                    break;
-                }
-            }
-        } else {
-            const double lrate = 1.0 + u01(rng_key(seed, iter, gc, rng::KEY_UPDATE)) * slr;
-            sc = scale[0];
-            const double e = ema[0];
-            if (e < 0.952381 * target) {
-                sc /= lrate;
-                sc = (sc > 1e-4) ? sc : 1e-4;
-            } else if (e > 1.05 * target) {
-                sc *= lrate;
-                sc = (sc < 10.0) ? sc : 10.0;
-            }
-            if (lane == 0) scale[0] = sc;
-            upd = 0;
-            sel = 0;
-        }
-        double t_scale = 1.0;
-        if (P.t_dof > 0.0) {
-            const double wg = gamma_draw(0.5 * P.t_dof, 0.5 * P.t_dof, seed, iter, gc);
-            t_scale = 1.0 / sqrt(wg);
-        }
-        const double* Ls = chol + (int64_t)sel * s * s + (int64_t)lb * s;
-        const double z = normal01(seed, iter, gc, lb);
-        const double f = t_scale * ((sel == upd) ? sc : scale[sel]);
-        double x = 0.0;
-        for (int j = 0; j < s; j++) {
-            const double zj = lane_bcast(z, j);
-            const double a = x + Ls[j] * zj;
-            x = (j <= lane) ? a : x;
-        }
-        const double newb = reflect(x * f + curb, P.lower[var], P.upper[var]);
-        if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE && s <= 16) {
-            double r = 0.0, qv = 0.0;
-            for (int k = 0; k < K; k++) {
-                const double sk = (k == upd) ? sc : scale[k];
-                const double ta0 = onb ? newb - mean[k * s + lane] : 0.0;
-                const double tb0 = onb ? (newb - curb) / sk : 0.0;
-                double ta, tb;
-                wave_lower_solve2_reg<16>(s, chol + (int64_t)k * s * s + (int64_t)lb * s, ta0, tb0, lane, ta, tb);
-                const double rk = (logc[k] - 0.5 * wave_seq_sum(s, onb ? ta * ta : 0.0)) + log(w[k]);
-                r = (lane == k) ? rk : r;
-                const double q = 0.5 * wave_seq_sum(s, onb ? tb * tb : 0.0);
-                qv = (lane == k) ? q : qv;
-            }
-            double lsum;
-            const double rr = wave_normalize_resp(K, r, lsum);
-            double fwd = -INFINITY, rev = -INFINITY;
-            for (int k = 0; k < K; k++) {
-                const double sk = (k == upd) ? sc : scale[k];
-                const double base = -log(sk * sk) + logc[k];
-                const double q = lane_bcast(qv, k);
-                fwd = logsum2(fwd, (base - q) + log(lane_bcast(rf, k)));
-                rev = logsum2(rev, (base - q) + log(lane_bcast(rr, k)));
-            }
-            lmh = rev - fwd;
-        } else if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
-            const double rr = wave_responsibilities(K, s, newb, mean, chol, logc, w, lane);
-            double fwd = -INFINITY, rev = -INFINITY;
-            for (int k = 0; k < K; k++) {
-                const double sk = (k == upd) ? sc : scale[k];
-                const double t0 = onb ? (newb - curb) / sk : 0.0;
-                const double t = wave_lower_solve(s, chol + (int64_t)k * s * s + (int64_t)lb * s, t0, lane);
-                const double base = -log(sk * sk) + logc[k];
-                const double q = 0.5 * wave_seq_sum(s, onb ? t * t : 0.0);
-                fwd = logsum2(fwd, (base - q) + log(lane_bcast(rf, k)));
-                rev = logsum2(rev, (base - q) + log(lane_bcast(rr, k)));
-            }
-            lmh = rev - fwd;
-        }
+        const block_draw b = wave_block_draw<false>(s, curb, P.lower + var, P.upper + var, P,
+                                                    blocked_state(P, B, c, d, m, o), 0.0, seed, iter, gc);
+        lmh = b.log_mh;
         // the block's new coordinates into the full vector (lane = variable), the rest unchanged
         for (int j = 0; j < s; j++) {
             const int vj = lane_bcast_i(var, j);
-            const double xj = lane_bcast(newb, j);
+            const double xj = lane_bcast(b.x, j);
             nxt = (lane == vj) ? xj : nxt;
         }
-        if (dir) {
-            // Dirichlet residual after the MH ratio of the unmodified proposal (SamplerPTChain.cpp:270-278);
-            // the residual may lie outside the block
-            for (int f = 0; f < d; f++) {
-                if (kind[f] != BCM3HIP_PRIOR_DIRICHLET || (int)p1[f] != f) continue;
-                const int l = prior::dirichlet_last(d, kind, p1, f);
-                double sum = 0.0;
-                for (int j = f; j < l; j++) sum += lane_bcast(nxt, j);
-                if (lane == l) nxt = 1.0 - sum;
-            }
-        }
-        if (lane == 0) B.selected[cb] = sel;
+        // (the residual may lie outside the block)
+        if (dir) nxt = wave_dirichlet_residual(d, kind, p1, nxt);
+        if (lane == 0) B.selected[(int64_t)c * d + m] = b.sel;
     }
     if (on) prop[(int64_t)c * d + lane] = nxt;
-    double lp;
-    if (!dir) {
-        lp = wave_seq_sum(d, on ? prior::log_pdf(kind[li], p0[li], p1[li], p2[li], nxt) : 0.0);
-    } else {
-        const double ul = (on && kind[li] != BCM3HIP_PRIOR_DIRICHLET) ? prior::log_pdf(kind[li], p0[li], p1[li], p2[li], nxt)
-                                                                        : 0.0;
-        lp = 0.0;
-        for (int f = 0; f < d; f++)
-            if (kind[f] == BCM3HIP_PRIOR_DIRICHLET && (int)p1[f] == f)
-                lp += prior::dirichlet_log_pdf(f, prior::dirichlet_last(d, kind, p1, f), p0, p2[f],
-                                               [&](int j) { return lane_bcast(nxt, j); });
-        for (int i = 0; i < d; i++)
-            if (kind[i] != BCM3HIP_PRIOR_DIRICHLET) lp += lane_bcast(ul, i);
-    }
+    const double lp = wave_log_prior(d, kind, p0, p1, p2, dir, nxt);
     if (lane == 0) {
         lprior_prop[c] = lp;
         log_mh[c] = lmh;
@@ -952,9 +902,9 @@ __device__ __forceinline__ double wave_seq_sum_from(double acc, int n, double x)
 }
 
 // ptmh_propose_blocked_kernel for 64 < d <= BCM3HIP_BLOCKED_MAX_D: one wavefront per chain and the
-// same two index spaces. The block (s <= 64) stays lane j = position j with the arithmetic, helpers
-// and RNG slots of the kernel above, so a block's proposal does not depend on the variables outside
-// it. The full vector is staged in LDS (xs, 8 KB): variable i is handled by lane i % 64 in pass
+// same two index spaces. The block (s <= 64) stays lane j = position j and is drawn by the same
+// wave_block_draw call as in the kernel above, so a block's proposal does not depend on the variables
+// outside it. The full vector is staged in LDS (xs, 8 KB): variable i is handled by lane i % 64 in pass
 // i / 64 -- the copy, the T = 0 prior draws (slot = variable), the scatter of the block's new
 // coordinates (a block's variables may lie in any pass), the Dirichlet sums, which read xs in
 // variable order across pass boundaries, and the log prior, summed left to right over 0 .. d-1
@@ -1020,119 +970,11 @@ __global__ void __launch_bounds__(64) ptmh_propose_blocked_wide_kernel(
         int var = B.block_vars[(int64_t)c * d + o + lb];
         var = (var < 0) ? 0 : ((var > d - 1) ? d - 1 : var);
         const double curb = vrow[var];
-        const int Km = P.kmax;
-        const int64_t cb = (int64_t)c * d + m;
-        int K = (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) ? B.ncomp[cb] : 1;
-        K = (K < 1) ? 1 : ((K > Km) ? Km : K);
-        double* scale = B.scale + cb * Km;
-        const double* ema = B.ema + cb * Km;
-        const double* logc = B.logc + cb * Km;
-        const double* w = B.weights + cb * Km;
-        const double* mean = B.mean + (int64_t)c * Km * d + (int64_t)Km * o;
-        const double* chol = B.chol + (int64_t)c * Km * d * d + (int64_t)Km * o * d;
-        const double slr = P.scaling_learning_rate;
-        const double target = B.target[cb];
-        int sel;
-        double rf = 0.0;
-        int upd = -1;
-        double sc = 0.0;
-        if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
-            const int last = B.selected[cb];
-            if (last != -1) {
-                const double lrate = 1.0 + u01(rng_key(seed, iter, gc, rng::KEY_UPDATE)) * slr * K;
-                sc = scale[last];
-                const double e = ema[last];
-                if (e < target / (1.0 - slr)) {
-                    sc /= lrate;
-                    sc = (sc > 1e-4) ? sc : 1e-4;
-                } else if (e > (1 + slr) * target) {
-                    sc *= lrate;
-                    sc = (sc < 10.0) ? sc : 10.0;
-                }
-                if (lane == 0) scale[last] = sc;
-                upd = last;
-            }
-            rf = wave_responsibilities(K, s, curb, mean, chol, logc, w, lane);
-            const double u = u01(rng_key(seed, iter, gc, rng::KEY_SELECT));
-            double acc = 0.0;
-            sel = K - 1;
-            for (int k = 0; k < K; k++) {
-                acc += lane_bcast(rf, k);
-                if (u < acc) {
-                    sel = k;
-                    break;
-                }
-            }
-        } else {
-            const double lrate = 1.0 + u01(rng_key(seed, iter, gc, rng::KEY_UPDATE)) * slr;
-            sc = scale[0];
-            const double e = ema[0];
-            if (e < 0.952381 * target) {
-                sc /= lrate;
-                sc = (sc > 1e-4) ? sc : 1e-4;
-            } else if (e > 1.05 * target) {
-                sc *= lrate;
-                sc = (sc < 10.0) ? sc : 10.0;
-            }
-            if (lane == 0) scale[0] = sc;
-            upd = 0;
-            sel = 0;
-        }
-        double t_scale = 1.0;
-        if (P.t_dof > 0.0) {
-            const double wg = gamma_draw(0.5 * P.t_dof, 0.5 * P.t_dof, seed, iter, gc);
-            t_scale = 1.0 / sqrt(wg);
-        }
-        const double* Ls = chol + (int64_t)sel * s * s + (int64_t)lb * s;
-        const double z = normal01(seed, iter, gc, lb);
-        const double f = t_scale * ((sel == upd) ? sc : scale[sel]);
-        double x = 0.0;
-        for (int j = 0; j < s; j++) {
-            const double zj = lane_bcast(z, j);
-            const double a = x + Ls[j] * zj;
-            x = (j <= lane) ? a : x;
-        }
-        const double newb = reflect(x * f + curb, P.lower[var], P.upper[var]);
-        if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE && s <= 16) {
-            double r = 0.0, qv = 0.0;
-            for (int k = 0; k < K; k++) {
-                const double sk = (k == upd) ? sc : scale[k];
-                const double ta0 = onb ? newb - mean[k * s + lane] : 0.0;
-                const double tb0 = onb ? (newb - curb) / sk : 0.0;
-                double ta, tb;
-                wave_lower_solve2_reg<16>(s, chol + (int64_t)k * s * s + (int64_t)lb * s, ta0, tb0, lane, ta, tb);
-                const double rk = (logc[k] - 0.5 * wave_seq_sum(s, onb ? ta * ta : 0.0)) + log(w[k]);
-                r = (lane == k) ? rk : r;
-                const double q = 0.5 * wave_seq_sum(s, onb ? tb * tb : 0.0);
-                qv = (lane == k) ? q : qv;
-            }
-            double lsum;
-            const double rr = wave_normalize_resp(K, r, lsum);
-            double fwd = -INFINITY, rev = -INFINITY;
-            for (int k = 0; k < K; k++) {
-                const double sk = (k == upd) ? sc : scale[k];
-                const double base = -log(sk * sk) + logc[k];
-                const double q = lane_bcast(qv, k);
-                fwd = logsum2(fwd, (base - q) + log(lane_bcast(rf, k)));
-                rev = logsum2(rev, (base - q) + log(lane_bcast(rr, k)));
-            }
-            lmh = rev - fwd;
-        } else if (P.kind == BCM3HIP_PROPOSAL_GAUSSIAN_MIXTURE) {
-            const double rr = wave_responsibilities(K, s, newb, mean, chol, logc, w, lane);
-            double fwd = -INFINITY, rev = -INFINITY;
-            for (int k = 0; k < K; k++) {
-                const double sk = (k == upd) ? sc : scale[k];
-                const double t0 = onb ? (newb - curb) / sk : 0.0;
-                const double t = wave_lower_solve(s, chol + (int64_t)k * s * s + (int64_t)lb * s, t0, lane);
-                const double base = -log(sk * sk) + logc[k];
-                const double q = 0.5 * wave_seq_sum(s, onb ? t * t : 0.0);
-                fwd = logsum2(fwd, (base - q) + log(lane_bcast(rf, k)));
-                rev = logsum2(rev, (base - q) + log(lane_bcast(rr, k)));
-            }
-            lmh = rev - fwd;
-        }
+        const block_draw b = wave_block_draw<false>(s, curb, P.lower + var, P.upper + var, P,
+                                                    blocked_state(P, B, c, d, m, o), 0.0, seed, iter, gc);
+        lmh = b.log_mh;
         // the block's new coordinates into the full vector (var is clamped to [0, d - 1]), the rest unchanged
-        if (onb) xs[var] = newb;
+        if (onb) xs[var] = b.x;
         __syncthreads();
         if (dir) {
             // Dirichlet residual after the MH ratio of the unmodified proposal (SamplerPTChain.cpp:270-278);
@@ -1147,7 +989,7 @@ __global__ void __launch_bounds__(64) ptmh_propose_blocked_wide_kernel(
                 __syncthreads();
             }
         }
-        if (lane == 0) B.selected[cb] = sel;
+        if (lane == 0) B.selected[(int64_t)c * d + m] = b.sel;
     }
     double lp = 0.0;
     if (dir) {
@@ -1179,55 +1021,6 @@ __global__ void __launch_bounds__(64) ptmh_propose_blocked_wide_kernel(
     }
 }
 
-// accept_one for a blocked move: the component that proposed and its acceptance EMA are the block's
-// (sel_p, ema_row)
-__device__ __forceinline__ bool accept_block_one(int c, int d, const double* __restrict__ temps, const double* __restrict__ prop,
-                           const double* __restrict__ lprior_prop, const double* __restrict__ llh_prop,
-                           const double* __restrict__ log_mh, double learning_rate, double* __restrict__ values,
-                           double* __restrict__ lprior, double* __restrict__ llh, double* __restrict__ lpp,
-                           uint8_t* __restrict__ acc_out, unsigned long long* __restrict__ accepted,
-                           int32_t* __restrict__ nan_llh, const int32_t* sel_p, double* ema_row, double ema_period,
-                           int64_t chain0, uint64_t seed, uint64_t iter)
-{
-    const double T = temps[c];
-    const double nl = llh_prop[c] * learning_rate;  // Sampler::EvaluateLikelihood
-    const double nq = lprior_prop[c];
-    bool acc;
-    double npp;
-    if (isnan(nl)) {
-        // Sampler::EvaluateLikelihood (Sampler.cpp:172-178): a NaN log-likelihood is fatal; the
-        // chain keeps its state (no EMA update) and the host raises at its next check of the flag
-        if (nan_llh) *nan_llh = 1;
-        acc = false;
-        npp = 0.0;
-    } else if (T == 0.0) {
-        acc = true;
-        npp = (nl == -INFINITY) ? nq : nq + T * nl;
-    } else {
-        npp = nq + T * nl;
-        acc = false;
-        if (npp > -INFINITY) {
-            double tp = npp - lpp[c];
-            tp = exp(tp + log_mh[c]);
-            tp = (tp < 1.0) ? tp : 1.0;  // std::min((Real)1.0, tp): NaN -> 1
-            acc = u01(rng_key(seed, iter, (uint64_t)(chain0 + c), rng::KEY_ACCEPT)) < tp;
-        }
-        // NotifyAccepted (EMA of the acceptance of the component that proposed)
-        const int sel = *sel_p;
-        double* ema = ema_row + sel;
-        const double alpha = 2.0 / (ema_period + 1);
-        *ema += ((acc ? 1.0 : 0.0) - *ema) * alpha;
-    }
-    if (acc) {
-        copy_row(values + (int64_t)c * d, prop + (int64_t)c * d, d);
-        lprior[c] = nq;
-        llh[c] = nl;
-        lpp[c] = npp;
-    }
-    if (acc_out) acc_out[c] = acc ? 1 : 0;
-    if (accepted && acc) atomicAdd(accepted, 1ull);
-    return acc;
-}
 
 __global__ void ptmh_accept_blocked_kernel(int C, int d, int m, const double* __restrict__ temps,
                                            const double* __restrict__ prop, const double* __restrict__ lprior_prop,
@@ -1247,9 +1040,9 @@ __global__ void ptmh_accept_blocked_kernel(int C, int d, int m, const double* __
     }
     // (an active T == 0 chain has m == 0 and reads neither the selection nor the EMAs)
     const int64_t cb = (int64_t)c * d + m;
-    accept_block_one(c, d, temps, prop, lprior_prop, llh_prop, log_mh, learning_rate, values, lprior, llh, lpp, acc_out,
-                     accepted, nan_llh, B.selected + cb, B.ema + cb * P.kmax, P.scaling_ema_period, chain0,
-                submove_seed(seed, m), iter);
+    accept_one(c, d, temps, prop, lprior_prop, llh_prop, log_mh, learning_rate, values, lprior, llh, lpp, acc_out,
+               accepted, nan_llh, B.selected + cb, B.ema + cb * P.kmax, P.scaling_ema_period, chain0,
+               submove_seed(seed, m), iter);
 }
 
 // SampleHistory::AddSample for the chains with T != 0 (and mask[c] != 0 when a mask is given):
@@ -1282,7 +1075,7 @@ __global__ void history_add_kernel(int C, int d, int H, int subsampling, const d
 // ---- speculative iteration pairs (include/bcm3hip.h "speculative iteration pairs") ----
 
 // Proposal::Update's branch for an acceptance EMA e: 0 shrink, 1 keep, 2 grow (the comparisons of
-// propose_wave_one, in the same form)
+// wave_block_draw, in the same form)
 __device__ __forceinline__ int update_branch(const bcm3hip_proposal& P, double e)
 {
     const double slr = P.scaling_learning_rate, target = P.target_acceptance;
@@ -1693,7 +1486,8 @@ __device__ __forceinline__ void commit_one(int c, int C, int d, int select, cons
         select_one(c, d, temps, partner, pair_first, acc_prev, acc_exc, cross_acc, remote, values, S, prop, lprior_prop,
                    log_mh, llh_prop, P, error);
     const bool acc = accept_one(c, d, temps, prop, lprior_prop, llh_prop, log_mh, learning_rate, values, lprior, llh,
-                                lpp, acc_out, accepted, nan_llh, P, chain0, seed, iter);
+                                lpp, acc_out, accepted, nan_llh, P.selected + c, P.ema + (int64_t)c * P.kmax,
+                                P.scaling_ema_period, chain0, seed, iter);
     if (acc) S.steps_hint[c] = S.steps_prop[c];
     if (hist) history_one(c, d, H, subsampling, temps, values, nullptr, hist, counters);
 }
