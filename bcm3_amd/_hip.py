@@ -20,6 +20,7 @@ ANALYTIC_BANANA, ANALYTIC_CIRCULAR, ANALYTIC_DUMMY = 1, 2, 3
 MIXTURE_NORMAL, MIXTURE_T = 1, 2
 OPT_LANES_PER_WAVE, OPT_BLOCK_WAVES, OPT_TIMING_LOG, OPT_UNI_SOLVER, OPT_BLOCK_LDS = 1, 2, 3, 4, 5
 OPT_PLACEMENT_LOG = 6
+OPT_CCM_ONE_LANE = 7
 PRIOR_UNIFORM, PRIOR_NORMAL = 0, 1
 PROPOSAL_GLOBAL_COVARIANCE, PROPOSAL_GAUSSIAN_MIXTURE = 0, 1
 PROPOSAL_KMAX = 16
@@ -127,6 +128,26 @@ def log_pdf_tnu3(x: float, mu: float, sigma: float) -> float:
     return lib().bcm3hip_log_pdf_tnu3(x, mu, sigma)
 
 
+CCM_NVARS = 10        # BCM3HIP_CCM_NVARS
+
+
+class CcmModel(C.Structure):
+    """bcm3hip_ccm_model (host pointer)"""
+    _fields_ = [("T", C.c_int32), ("data", C.c_void_p)]
+
+
+def cell_cycle_marker_host(data, values) -> np.ndarray:
+    """bcm3hip_cell_cycle_marker_host: the cell_cycle_marker kernel's source compiled for the host --
+    logp [n] of values [n, 10] against the track data [T]. Needs no device."""
+    t = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, CCM_NVARS)
+    logp = np.empty(v.shape[0])
+    m = CcmModel(t.size, t.ctypes.data)
+    check(lib().bcm3hip_cell_cycle_marker_host(C.byref(m), v.shape[0], v.ctypes.data, logp.ctypes.data),
+          "bcm3hip_cell_cycle_marker_host")
+    return logp
+
+
 STATS_DTYPE = np.dtype([(k, np.int32) for k in ("nst", "nfe", "nni", "nsetups", "nje", "netf", "ncfn", "nreinit")])
 
 _lib = None
@@ -199,6 +220,10 @@ def lib() -> C.CDLL:
     L.bcm3hip_incucyte_variable_name.restype = C.c_char_p
     L.bcm3hip_log_pdf_tnu3.argtypes = [C.c_double, C.c_double, C.c_double]
     L.bcm3hip_log_pdf_tnu3.restype = C.c_double
+    L.bcm3hip_open_cell_cycle_marker.argtypes = [C.c_int, C.POINTER(CcmModel), C.POINTER(vp)]
+    L.bcm3hip_open_cell_cycle_marker.restype = C.c_int
+    L.bcm3hip_cell_cycle_marker_host.argtypes = [C.POINTER(CcmModel), i64, vp, vp]
+    L.bcm3hip_cell_cycle_marker_host.restype = C.c_int
     for f in ("bcm3hip_open_popk", "bcm3hip_open_analytic", "bcm3hip_open_mixture", "bcm3hip_open_expm_pk", "bcm3hip_close", "bcm3hip_set_option",
               "bcm3hip_num_variables", "bcm3hip_eval_batch", "bcm3hip_eval_batch_device",
               "bcm3hip_last_kernel_ms", "bcm3hip_eval_batch_detail"):
@@ -316,6 +341,16 @@ class Context:
         h = C.c_void_p()
         check(lib().bcm3hip_open_expm_pk(device, C.byref(m), C.byref(h)), "bcm3hip_open_expm_pk")
         return cls(h, int(m.d))
+
+    @classmethod
+    def cell_cycle_marker(cls, data, device: int = 0) -> "Context":
+        """bcm3hip_open_cell_cycle_marker: data [T] is one fluorescence track (NaN = not observed),
+        uploaded once."""
+        t = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
+        m = CcmModel(t.size, t.ctypes.data)
+        h = C.c_void_p()
+        check(lib().bcm3hip_open_cell_cycle_marker(device, C.byref(m), C.byref(h)), "bcm3hip_open_cell_cycle_marker")
+        return cls(h, CCM_NVARS, T=int(t.size))
 
     def set_option(self, opt: int, value: int):
         check(lib().bcm3hip_set_option(self.h, opt, int(value)), "bcm3hip_set_option")

@@ -16,6 +16,7 @@
 
 #include "../../include/bcm3hip.h"
 #include "libm_exact.h"
+#include "ccm_kernel.h"
 #include "incucyte_kernel.h"
 #include "popk_kernel.h"
 
@@ -43,7 +44,9 @@ inline bool cp_assign_lds_fits(int n) { return cp_assign_ws_bytes(n) <= 52 * 102
 
 struct bcm3hip_ctx {
     int device = 0;
-    int kind = 0;  // 1 popk, 2 analytic, 3 expm pk, 4 cell population, 5 incucyte population
+    int kind = 0;  // 1 popk, 2 analytic, 3 expm pk, 4 cell population, 5 incucyte population, 6 cell cycle marker
+    CcmDevModel cm{};
+    bool ccm_one_lane = false;  // BCM3HIP_OPT_CCM_ONE_LANE
     IncucyteDevModel im{};
     // incucyte scratch, grow-only: simulated wells, CTB, per-well step counts / return codes /
     // counters, and the step history of one chunk of items
@@ -642,6 +645,27 @@ int bcm3hip_open_incucyte(int device, const bcm3hip_incucyte_model* m, bcm3hip_c
     return 0;
 }
 
+int bcm3hip_open_cell_cycle_marker(int device, const bcm3hip_ccm_model* m, bcm3hip_ctx** out)
+{
+    if (!m || !out) return BCM3HIP_ERR_ARG;
+    *out = nullptr;
+    if (m->T < 1) return BCM3HIP_ERR_MODEL;
+    if (!m->data) return BCM3HIP_ERR_ARG;
+    bcm3hip_ctx* c = new (std::nothrow) bcm3hip_ctx();
+    if (!c) return BCM3HIP_ERR_ALLOC;
+    int r = ctx_common_init(c, device);
+    if (r == 0) r = upload(c, m->data, (size_t)m->T, &c->cm.data);
+    if (r) {
+        bcm3hip_close(c);
+        return r;
+    }
+    c->kind = 6;
+    c->d = BCM3HIP_CCM_NVARS;
+    c->cm.T = m->T;
+    *out = c;
+    return 0;
+}
+
 int bcm3hip_close(bcm3hip_ctx* c)
 {
     if (!c) return 0;
@@ -704,6 +728,10 @@ int bcm3hip_set_option(bcm3hip_ctx* c, int option, int64_t value)
     case BCM3HIP_OPT_PLACEMENT_LOG:
         if (value != 0 && value != 1) return BCM3HIP_ERR_ARG;
         c->place_log = value != 0;
+        return 0;
+    case BCM3HIP_OPT_CCM_ONE_LANE:
+        if (c->kind != 6 || (value != 0 && value != 1)) return BCM3HIP_ERR_ARG;
+        c->ccm_one_lane = value != 0;
         return 0;
     default: return BCM3HIP_ERR_ARG;
     }
@@ -858,6 +886,8 @@ static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp
             e = bcm3hip::launch_cp_accumulate((int32_t)n, dlogp, st, c->cp_logp, c->cp_status, s);
         }
         if (e == hipSuccess && e1 && !c->cp_more.empty()) e = hipEventRecord(e1, s);
+    } else if (c->kind == 6) {
+        e = launch_ccm(c->cm, (int64_t)n, dvalues, dlogp, dstatus, c->ccm_one_lane, s, e0, e1);
     } else {
         e = launch_analytic(c->am, (int64_t)n, dvalues, dlogp, dstatus, s, e0, e1);
     }

@@ -1,0 +1,19 @@
+// ccm_kernel.h -- device-side model and launcher of the cell_cycle_marker likelihood (internal to
+// libbcm3hip.so; ccm_kernel.hip, arithmetic in ccm_model.h).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace bcm3hip {
+
+struct CcmDevModel {
+    int32_t T;           // observations of the track, >= 1
+    const double* data;  // [T] in device memory, NaN = not observed
+};
+
+// one_lane: the one-lane-per-evaluation variant (BCM3HIP_OPT_CCM_ONE_LANE), same results
+hipError_t launch_ccm(const CcmDevModel& m, int64_t n, const double* values, double* logp, int32_t* status,
+                      bool one_lane, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop);
+
+}  // namespace bcm3hip

@@ -1,5 +1,6 @@
 // Likelihood.cpp -- bcm3::Likelihood defaults (src/sampler/Likelihood.cpp:1-44) and the factory.
 #include "Likelihood.h"
+#include "LikelihoodCellCycleMarker.h"
 #include "LikelihoodCellPopulation.h"
 
 #include <cmath>
@@ -59,7 +60,7 @@ std::string option_get(const OptionsMap& vm, const std::string& key, const std::
 std::vector<std::string> LikelihoodFactory::SupportedTypes()
 {
     return {"pop_pk_trajectory", "pharmacokinetic_trajectory", "pharmaco_single", "pharmaco_population", "banana", "circular",
-            "multimodal_gaussians", "truncated_t", "dummy", "cell_population", "incucyte_population", "dll"};
+            "multimodal_gaussians", "truncated_t", "dummy", "cell_population", "incucyte_population", "cell_cycle_marker", "dll"};
 }
 
 std::shared_ptr<Likelihood> LikelihoodFactory::CreateLikelihood(const std::string& fn,
@@ -114,10 +115,12 @@ std::shared_ptr<Likelihood> LikelihoodFactory::CreateLikelihood(const std::strin
         ll = std::make_shared<LikelihoodCellPopulation>(sampling_threads, evaluation_threads);
     } else if (type == "incucyte_population") {
         ll = std::make_shared<LikelihoodIncucytePopulation>(sampling_threads, evaluation_threads);
+    } else if (type == "cell_cycle_marker") {
+        ll = std::make_shared<LikelihoodCellCycleMarker>(sampling_threads, evaluation_threads);
     } else if (type == "dll") {
         ll = std::make_shared<LikelihoodDLL>(sampling_threads, evaluation_threads);
     } else {
-        LOGERROR("Unknown likelihood type \"%s\" (supported on this backend: pop_pk_trajectory, pharmacokinetic_trajectory, pharmaco_single, pharmaco_population, banana, circular, multimodal_gaussians, truncated_t, dummy, cell_population, incucyte_population, dll)",
+        LOGERROR("Unknown likelihood type \"%s\" (supported on this backend: pop_pk_trajectory, pharmacokinetic_trajectory, pharmaco_single, pharmaco_population, banana, circular, multimodal_gaussians, truncated_t, dummy, cell_population, incucyte_population, cell_cycle_marker, dll)",
                  type.c_str());
         return ll;
     }

@@ -12,6 +12,8 @@
 #include "log.h"
 
 #include "capi_internal.h"
+#include "CSVParser.h"
+#include "LikelihoodCellCycleMarker.h"
 #include "LikelihoodCellPopulation.h"
 #include "LikelihoodIncucyte.h"
 
@@ -144,6 +146,29 @@ int bcm3_likelihood_incucyte_detail(bcm3_likelihood* h, size_t n, const double* 
     if (!p || !p->Context()) return -2;
     return bcm3hip_eval_batch_incucyte_detail(p->Context(), n, p->GetNumVariables(), values, logp, status, wells, ctb,
                                               steps, codes);
+}
+
+int64_t bcm3_likelihood_ccm_track(const bcm3_likelihood* h, double* data, int64_t cap, int32_t* track_ix)
+{
+    if (!h || !h->ll) return -1;
+    auto* p = dynamic_cast<bcm3::LikelihoodCellCycleMarker*>(h->ll.get());
+    if (!p) return -2;
+    const std::vector<double>& t = p->GetTrack();
+    if (data && cap > 0) std::copy(t.begin(), t.begin() + std::min<size_t>((size_t)cap, t.size()), data);
+    if (track_ix) *track_ix = p->GetTrackIndex();
+    return (int64_t)t.size();
+}
+
+int64_t bcm3_table_read(const char* filename, const char* sep, int64_t* columns, double* values, int64_t cap)
+{
+    if (!filename || !sep) return -1;
+    bcm3::CSVParser parser;
+    if (!parser.Parse(filename, sep)) return -2;
+    const size_t rows = parser.GetNumRows(), cols = parser.GetNumColumns();
+    if (columns) *columns = (int64_t)cols;
+    for (size_t k = 0; values && k < rows * cols && k < (size_t)std::max<int64_t>(cap, 0); k++)
+        values[k] = parser.GetEntry(k / cols, k % cols);
+    return (int64_t)rows;
 }
 
 void bcm3_likelihood_destroy(bcm3_likelihood* h) { delete h; }

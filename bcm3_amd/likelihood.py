@@ -33,6 +33,10 @@ def lib() -> C.CDLL:
     L.bcm3_likelihood_expm_pk_model.argtypes = [vp, C.POINTER(_hip.ExpmPKModel)]
     L.bcm3_likelihood_incucyte_model.argtypes = [vp, C.POINTER(_hip.IncucyteModel)]
     L.bcm3_likelihood_incucyte_detail.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.bcm3_likelihood_ccm_track.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int32)]
+    L.bcm3_likelihood_ccm_track.restype = C.c_int64
+    L.bcm3_table_read.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_int64), vp, C.c_int64]
+    L.bcm3_table_read.restype = C.c_int64
     L.bcm3_likelihood_destroy.argtypes = [vp]
     L.bcm3_likelihood_destroy.restype = None
     L.bcm3_likelihood_num_variables.argtypes = [vp]
@@ -61,6 +65,19 @@ def lib() -> C.CDLL:
 
 def _err(what: str, code: int):
     raise RuntimeError(f"{what} failed ({code}): {lib().bcm3_last_error().decode()}")
+
+
+def read_table(filename: str, sep: str = "\t") -> np.ndarray:
+    """bcm3::CSVParser::Parse(filename, sep) with row names (bcm3_table_read): the values [rows,
+    columns] of a separated-value table whose header line and first column are names."""
+    cols = C.c_int64()
+    rows = lib().bcm3_table_read(filename.encode(), sep.encode(), C.byref(cols), None, 0)
+    if rows < 0:
+        _err("bcm3_table_read", rows)
+    out = np.empty((rows, cols.value))
+    if out.size:
+        lib().bcm3_table_read(filename.encode(), sep.encode(), C.byref(cols), out.ctypes.data, out.size)
+    return out
 
 
 class Likelihood:
@@ -144,6 +161,17 @@ class Likelihood:
         if r != 0:
             _err("bcm3_likelihood_incucyte_detail", r)
         return out
+
+    def ccm_track(self):
+        """cell_cycle_marker: (track index, the track's frames [T]) the likelihood evaluates against
+        (bcm3_likelihood_ccm_track)."""
+        ix = C.c_int32()
+        n = lib().bcm3_likelihood_ccm_track(self.h, None, 0, C.byref(ix))
+        if n < 0:
+            _err("bcm3_likelihood_ccm_track", n)
+        out = np.empty(n)
+        lib().bcm3_likelihood_ccm_track(self.h, out.ctypes.data, n, None)
+        return ix.value, out
 
     def generated_code(self) -> str:
         """cell_population: the generated_derivative body this likelihood compiled (SBMLModel::GenerateCode)."""

@@ -48,6 +48,17 @@ int bcm3_likelihood_incucyte_model(const bcm3_likelihood* ll, void* model);
 /* bcm3hip_eval_batch_incucyte_detail on the likelihood's context (-2: another type, or no device) */
 int bcm3_likelihood_incucyte_detail(bcm3_likelihood* ll, size_t n, const double* values, double* logp, int32_t* status,
                                     double* wells, double* ctb, int32_t* steps, int32_t* codes);
+/* cell_cycle_marker: the track the likelihood evaluates against (the row ccm.track_ix selected):
+ * copies up to cap frames into data (may be NULL) and the row index into *track_ix (may be NULL);
+ * returns the number of frames, -2 for other likelihood types. */
+int64_t bcm3_likelihood_ccm_track(const bcm3_likelihood* ll, double* data, int64_t cap, int32_t* track_ix);
+/* bcm3::CSVParser::Parse(filename, sep) with row names (src/utils/CSVParser.cpp), the reader of the
+ * cell_cycle_marker track file: the header's first token and every row's first token are names, "NA"
+ * / "nan" in any letter case are NaN, everything else goes through atof. Returns the number of rows
+ * and stores the number of columns in *columns; values (may be NULL) receives up to cap entries,
+ * row-major. < 0 when the file cannot be opened, is empty or has a row of another length
+ * (bcm3_last_error). */
+int64_t bcm3_table_read(const char* filename, const char* sep, int64_t* columns, double* values, int64_t cap);
 /* cell_population: the generated_derivative body (SBMLModel::GenerateCode, src/sbml/SBMLModel.cpp:
  * 291-367) this likelihood compiled; returns its length (buf may be NULL), < 0 for other types */
 int bcm3_likelihood_generated_code(const bcm3_likelihood* ll, char* buf, size_t buflen);

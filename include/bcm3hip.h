@@ -391,6 +391,20 @@ typedef struct {
     const bcm3hip_incucyte_experiment* experiments; /* [E] */
 } bcm3hip_incucyte_model;
 
+/* ---- cell_cycle_marker likelihood (src/likelihoods/LikelihoodCellCycleMarker.cpp) --------------
+ * A piecewise-linear reporter signal against one fluorescence track, one observation per frame
+ * (frame index = time). The ten variables, in prior.xml order: S_entry_time, S_duration,
+ * plateau_duration, base_signal, S_signal_increase, plateau_signal_increase,
+ * mitosis_signal_fraction, mitosis_signal_decrease, additive_noise, proportional_noise. Frame i
+ * contributes LogPdfTnu4(data[i], x_i, additive + proportional * max(x_i, 0), skip_na = true); a
+ * zero or negative scale is not special-cased (the result is what IEEE arithmetic gives, a NaN as
+ * the quiet NaN 0x7ff8000000000000). */
+#define BCM3HIP_CCM_NVARS 10
+typedef struct {
+    int32_t T;          /* frames of the track (>= 1) */
+    const double* data; /* [T] observed signal, NaN = not observed */
+} bcm3hip_ccm_model;
+
 typedef struct bcm3hip_ctx bcm3hip_ctx;
 
 /* Per-trajectory solver counters (parity/diagnostics), one record per (item, patient). */
@@ -410,8 +424,11 @@ enum {
                                        default 0): caps the workgroups resident per CU, so a launch
                                        with more wavefronts than SIMDs queues the rest instead of
                                        sharing a SIMD */
-    BCM3HIP_OPT_PLACEMENT_LOG = 6   /* diagnostics, PopPK one-trajectory-per-wavefront launches: 1 = each
+    BCM3HIP_OPT_PLACEMENT_LOG = 6,  /* diagnostics, PopPK one-trajectory-per-wavefront launches: 1 = each
                                        trajectory records where and when it ran (see placement_log) */
+    BCM3HIP_OPT_CCM_ONE_LANE = 7    /* tests and measurements, cell_cycle_marker contexts: 1 = the
+                                       one-lane-per-evaluation kernel instead of one wavefront per
+                                       evaluation (default 0); same results */
 };
 
 int bcm3hip_device_count(void);
@@ -476,6 +493,14 @@ const char* bcm3hip_incucyte_variable_name(int which);
  * solve; codes[n][E][11] its return code (0, CVODE's CV_* code, BCM3HIP_INCUCYTE_HISTORY_FULL). */
 int bcm3hip_eval_batch_incucyte_detail(bcm3hip_ctx* ctx, size_t n, size_t d, const double* values, double* logp,
                                        int32_t* status, double* wells, double* ctb, int32_t* steps, int32_t* codes);
+/* cell_cycle_marker: the track is uploaded once; one wavefront evaluates one parameter vector, its
+ * lanes taking the frames 64 at a time, and the terms are added in frame order (the reference's
+ * serial sum, bit for bit the same as bcm3hip_cell_cycle_marker_host). status is 0 for every item.
+ * BCM3HIP_ERR_MODEL when T < 1. */
+int bcm3hip_open_cell_cycle_marker(int device, const bcm3hip_ccm_model* model, bcm3hip_ctx** out);
+/* the cell_cycle_marker kernel's source compiled for the host: logp[n] of values[n][10] against the
+ * model's track (host pointers). Host only, no device needed. */
+int bcm3hip_cell_cycle_marker_host(const bcm3hip_ccm_model* model, int64_t n, const double* values, double* logp);
 int bcm3hip_close(bcm3hip_ctx* ctx);
 int bcm3hip_set_option(bcm3hip_ctx* ctx, int option, int64_t value);
 int bcm3hip_num_variables(const bcm3hip_ctx* ctx);
