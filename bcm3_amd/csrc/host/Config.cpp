@@ -243,6 +243,23 @@ bool ConfigFile::Bool(const std::string& key) const
     return b;
 }
 
+// the likelihood factory's options, as bcm3_likelihood_create_ex's "key=value;..." string: only
+// those the file sets (the likelihoods apply the same defaults themselves)
+static bool LikelihoodOptions(const ConfigFile& cf, std::string& options)
+{
+    for (const char* key : {"pk.patient", "pharmacosingle.patient", "cellpop.use_only_cell_ix", "ccm.track_ix"}) {
+        if (!cf.Set(key)) continue;
+        const std::string& v = cf.String(key);
+        if (v.find(';') != std::string::npos) {
+            LOGERROR("%s: ';' is not allowed in a likelihood option value", key);
+            return false;
+        }
+        if (!options.empty()) options += ';';
+        options += std::string(key) + "=" + v;
+    }
+    return true;
+}
+
 bool LoadRunConfig(const std::string& path, RunConfig& out)
 {
     ConfigFile cf;
@@ -348,18 +365,53 @@ bool LoadRunConfig(const std::string& path, RunConfig& out)
     rc.likelihood = cf.String("likelihood");
     rc.output_folder = cf.String("output.folder");
 
-    // the likelihood factory's options, as bcm3_likelihood_create_ex's "key=value;..." string:
-    // only those the file sets (the likelihoods apply the same defaults themselves)
-    for (const char* key : {"pk.patient", "pharmacosingle.patient", "cellpop.use_only_cell_ix", "ccm.track_ix"}) {
-        if (!cf.Set(key)) continue;
-        const std::string& v = cf.String(key);
-        if (v.find(';') != std::string::npos) {
-            LOGERROR("%s: ';' is not allowed in a likelihood option value", key);
-            return false;
-        }
-        if (!rc.likelihood_options.empty()) rc.likelihood_options += ';';
-        rc.likelihood_options += std::string(key) + "=" + v;
+    if (!LikelihoodOptions(cf, rc.likelihood_options)) return false;
+    out = rc;
+    return true;
+}
+
+bool LoadISRunConfig(const std::string& path, ISRunConfig& out)
+{
+    ConfigFile cf;
+    if (!cf.Load(path)) return false;
+    ISRunConfig rc;
+    // SamplerFactory::Create (SamplerFactory.cpp:10-37)
+    rc.sampler_type = cf.String("sampler.type");
+    if (rc.sampler_type != "is" && rc.sampler_type != "importance_sampling") {
+        if (rc.sampler_type == "ptmh" || rc.sampler_type == "parallel_tempered_Metropolis_Hastings")
+            LOGERROR("sampler.type \"%s\": this is the importance sampler's reader; the PT-MH sampler reads its "
+                     "settings with bcm3_run_config_from_file",
+                     rc.sampler_type.c_str());
+        else
+            LOGERROR("Unknown sampler type \"%s\"", rc.sampler_type.c_str());
+        return false;
     }
+    // Sampler::LoadSettings (Sampler.cpp:55-62) + seeding (:91-94): 0 = a time-based seed
+    rc.num_samples = cf.Int("sampler.num_samples");
+    if (rc.num_samples < 1) {
+        LOGERROR("sampler.num_samples must be at least 1");
+        return false;
+    }
+    if (cf.Int("sampler.use_every_nth") != 1) {
+        // SamplerIS::RunImpl hands num_samples * use_every_nth samples to a file dimensioned for
+        // num_samples rows (SamplerIS.cpp:55, SampleHandlerNetCDF.cpp:34-47, 90-106)
+        LOGERROR("sampler.use_every_nth = %lld: the importance sampler keeps every accepted draw; the reference writes "
+                 "num_samples * use_every_nth samples into a file of num_samples rows, so only 1 is supported",
+                 (long long)cf.Int("sampler.use_every_nth"));
+        return false;
+    }
+    rc.seed = cf.ULL("sampler.rngseed");
+    if (rc.seed == 0) {
+        rc.seed = (uint64_t)std::chrono::high_resolution_clock::now().time_since_epoch().count();
+        LOG("sampler.rngseed = 0: using the time-based seed %llu", (unsigned long long)rc.seed);
+    }
+    // bcminf (main.cpp:47-58, 83-121); the ptmhsampler.* keys were type-checked by the parser and are
+    // not read
+    rc.learning_rate = cf.Real("learning_rate");
+    rc.prior = cf.String("prior");
+    rc.likelihood = cf.String("likelihood");
+    rc.output_folder = cf.String("output.folder");
+    if (!LikelihoodOptions(cf, rc.likelihood_options)) return false;
     out = rc;
     return true;
 }

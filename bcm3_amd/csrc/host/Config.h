@@ -57,4 +57,18 @@ struct RunConfig {
 // proposal_transform_to_unbounded).
 bool LoadRunConfig(const std::string& path, RunConfig& out);
 
+// What the importance sampler (SamplerISDevice) reads out of the same config.txt: Sampler::LoadSettings
+// (Sampler.cpp:55-62; SamplerIS::LoadSettings adds nothing, SamplerIS.cpp:17-32) and bcminf's options.
+struct ISRunConfig {
+    int64_t num_samples = 2500;
+    uint64_t seed = 0;
+    double learning_rate = 1.0;
+    std::string sampler_type, prior, likelihood, output_folder;
+    std::string likelihood_options;  // "key=value;..." (bcm3_likelihood_create_ex)
+};
+
+// sampler.type = is | importance_sampling only (ptmh is LoadRunConfig's); ptmhsampler.* keys are
+// parsed and ignored; sampler.use_every_nth != 1 is refused (DESIGN.md §4 "importance sampler")
+bool LoadISRunConfig(const std::string& path, ISRunConfig& out);
+
 }  // namespace bcm3

@@ -757,7 +757,7 @@ bool SampleFileWriter::InitializeNetCDF4(const std::string& filename, const std:
 }
 
 bool SampleFileWriter::Write(size_t sample_ix, size_t t0, size_t nt, const double* values, const double* lprior,
-                             const double* llh, const double* weight)
+                             const double* llh, const double* weight, bool keep_coordinate)
 {
     if (sample_ix >= n_ || t0 + nt > own_) return false;
     if (w4_) {
@@ -765,7 +765,7 @@ bool SampleFileWriter::Write(size_t sample_ix, size_t t0, size_t nt, const doubl
         // write over the 1-based coordinate), then the rows of these temperatures
         const uint32_t si = (uint32_t)sample_ix;
         const size_t t = t0;
-        return w4_->PutUInt(g4_, v_six_, {sample_ix}, {1}, &si) &&
+        return (keep_coordinate || w4_->PutUInt(g4_, v_six_, {sample_ix}, {1}, &si)) &&
                w4_->PutDouble(g4_, v_vals_, {sample_ix, t, 0}, {1, nt, d_}, values) &&
                w4_->PutDouble(g4_, v_lp_, {sample_ix, t}, {1, nt}, lprior) &&
                w4_->PutDouble(g4_, v_llh_, {sample_ix, t}, {1, nt}, llh) &&
@@ -773,7 +773,7 @@ bool SampleFileWriter::Write(size_t sample_ix, size_t t0, size_t nt, const doubl
     }
     const size_t t = first_ + t0;
     const int32_t si = (int32_t)sample_ix;
-    return (first_ != 0 || w_.PutInt(v_six_, {sample_ix}, {1}, &si)) &&
+    return (first_ != 0 || keep_coordinate || w_.PutInt(v_six_, {sample_ix}, {1}, &si)) &&
            w_.PutDouble(v_vals_, {sample_ix, t, 0}, {1, nt, d_}, values) &&
            w_.PutDouble(v_lp_, {sample_ix, t}, {1, nt}, lprior) && w_.PutDouble(v_llh_, {sample_ix, t}, {1, nt}, llh) &&
            w_.PutDouble(v_w_, {sample_ix, t}, {1, nt}, weight);

@@ -152,9 +152,11 @@ public:
     bool Initialize(const std::string& filename, size_t num_samples, const std::vector<std::string>& names,
                     const std::vector<int32_t>& transforms, const std::vector<double>& temperatures,
                     size_t first_temperature, size_t own);
-    // rows of this process's temperatures (t0 relative to first_temperature): values [own][d]
+    // rows of this process's temperatures (t0 relative to first_temperature): values [own][d].
+    // keep_coordinate: leave sample_ix[sample_ix] at the 1-based value of the file's creation (the
+    // importance sampler's output) instead of the reference handler's 0-based overwrite
     bool Write(size_t sample_ix, size_t t0, size_t nt, const double* values, const double* lprior,
-               const double* llh, const double* weight);
+               const double* llh, const double* weight, bool keep_coordinate = false);
     bool Sync() { return w4_ ? w4_->Sync() : w_.Sync(); }
     void Close()
     {

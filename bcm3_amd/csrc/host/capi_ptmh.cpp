@@ -52,16 +52,6 @@ void bcm3_ptmh_config_default(bcm3_ptmh_config* c)
     c->transport = BCM3_PTMH_TRANSPORT_NONE;
 }
 
-static bool CopyString(char* dst, size_t cap, const std::string& src, const char* what)
-{
-    if (src.size() + 1 > cap) {
-        LOGERROR("config: %s is longer than %zu characters", what, cap - 1);
-        return false;
-    }
-    std::memcpy(dst, src.c_str(), src.size() + 1);
-    return true;
-}
-
 int bcm3_run_config_from_file(const char* path, bcm3_run_config* out)
 {
     if (!path || !out) return -1;
@@ -93,11 +83,11 @@ int bcm3_run_config_from_file(const char* path, bcm3_run_config* out)
     r.output_proposal_adaptation = rc.output_proposal_adaptation ? 1 : 0;
     r.sampling_threads = rc.sampling_threads;
     r.evaluation_threads = rc.evaluation_threads;
-    if (!CopyString(r.sampler_type, sizeof(r.sampler_type), rc.sampler_type, "sampler.type") ||
-        !CopyString(r.prior, sizeof(r.prior), rc.prior, "prior") ||
-        !CopyString(r.likelihood, sizeof(r.likelihood), rc.likelihood, "likelihood") ||
-        !CopyString(r.output_folder, sizeof(r.output_folder), rc.output_folder, "output.folder") ||
-        !CopyString(r.likelihood_options, sizeof(r.likelihood_options), rc.likelihood_options, "likelihood options"))
+    if (!bcm3::CopyConfigString(r.sampler_type, sizeof(r.sampler_type), rc.sampler_type, "sampler.type") ||
+        !bcm3::CopyConfigString(r.prior, sizeof(r.prior), rc.prior, "prior") ||
+        !bcm3::CopyConfigString(r.likelihood, sizeof(r.likelihood), rc.likelihood, "likelihood") ||
+        !bcm3::CopyConfigString(r.output_folder, sizeof(r.output_folder), rc.output_folder, "output.folder") ||
+        !bcm3::CopyConfigString(r.likelihood_options, sizeof(r.likelihood_options), rc.likelihood_options, "likelihood options"))
         return -2;
     *out = r;
     return 0;

@@ -312,6 +312,52 @@ int bcm3_samples_write(bcm3_samples* h, int64_t sample_ix, int32_t t0, int32_t n
 int bcm3_samples_sync(bcm3_samples* h);
 void bcm3_samples_close(bcm3_samples* h);
 
+/* ---- the importance sampler (SamplerISDevice.cpp): sampler.type = is | importance_sampling ----
+ * SamplerIS::RunImpl (src/sampler/SamplerIS.cpp:49-87) in batches on the device: per round
+ * `batch` draws from the prior (bcm3hip_is_draw: draw g is the counter-based stream (seed, g)), one
+ * batched likelihood launch, the reference's weight rule in draw order (bcm3hip_is_filter: a draw is
+ * kept unless its log weight is more than 23.02585 below the highest seen so far), until num_samples
+ * draws are kept. The samples are identical for every batch size. Not thread-safe per handle. */
+typedef struct bcm3_is bcm3_is;
+typedef struct {
+    uint64_t seed;        /* sampler.rngseed */
+    double learning_rate; /* the log likelihood is multiplied by it (Sampler::EvaluateLikelihood) */
+    int64_t batch;        /* draws per round, 0 = 1024; a throughput setting only */
+} bcm3_is_config;
+void bcm3_is_config_default(bcm3_is_config* cfg);
+/* prior_xml: the prior.xml the likelihood was created with (PriorIndependence marginals, at most
+ * 1024 variables). The sampler runs on a stream of its own on the likelihood's device. */
+int bcm3_is_create(bcm3_likelihood* ll, const char* prior_xml, const bcm3_is_config* cfg, bcm3_is** out);
+/* The walk from draw 0 until num_samples draws are kept (each call starts over); < 0 when a
+ * likelihood returned NaN (Sampler.cpp:172-178). With bcm3_is_set_output the samples are then written. */
+int bcm3_is_run(bcm3_is* s, int64_t num_samples);
+int64_t bcm3_is_num_samples(const bcm3_is* s); /* of the last run */
+/* the last run's samples (any may be NULL): values[N][d], lprior[N], llh[N] (times the learning
+ * rate), weight[N] = exp(llh), unnormalised as the reference writes them */
+int bcm3_is_get_samples(bcm3_is* s, double* values, double* lprior, double* llh, double* weight);
+/* of the last run (any may be NULL): the draws the rule walked up to the one that became the last
+ * sample, the draws kept, the highest log weight, and the effective sample size (sum w)^2 / sum w^2 of
+ * the kept weights (scaled by exp(-highest)) */
+int bcm3_is_get_counters(bcm3_is* s, int64_t* draws_evaluated, int64_t* draws_kept, double* highest_log_weight,
+                         double* effective_sample_size);
+/* SampleHandlerNetCDF for this sampler: bcm3_is_run writes its samples to `filename` in the
+ * bcm3_samples_* format -- one temperature, 1.0; sample_ix 1..num_samples; weights filled */
+int bcm3_is_set_output(bcm3_is* s, const char* filename);
+void bcm3_is_destroy(bcm3_is* s);
+/* config.txt for this sampler, through the reader of bcm3_run_config_from_file (same options, same
+ * syntax rules): sampler.type must be is or importance_sampling (ptmh: bcm3_run_config_from_file),
+ * sampler.use_every_nth must be 1 (the reference would hand num_samples * use_every_nth samples to a
+ * file of num_samples rows), the ptmhsampler.* keys are parsed and ignored. `is.batch` is left at
+ * its default. */
+typedef struct {
+    bcm3_is_config is;
+    int64_t num_samples; /* sampler.num_samples (2500): bcm3_is_run's argument */
+    char sampler_type[64];
+    char prior[1024], likelihood[1024], output_folder[1024];
+    char likelihood_options[2048]; /* "key=value;..." for bcm3_likelihood_create_ex */
+} bcm3_is_run_config;
+int bcm3_is_config_from_file(const char* path, bcm3_is_run_config* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -871,6 +871,42 @@ int bcm3hip_nccl_exchange(void* comm, int n_send, const double* const* send, con
 int bcm3hip_eval_batch_detail(bcm3hip_ctx* ctx, size_t n, size_t d, const double* values, double* logp,
                               int32_t* status, double* patient_llh, double* traj, bcm3hip_traj_stats* stats);
 
+/* ---- Importance sampler (is_kernels.hip) ----
+ * SamplerIS::RunImpl (src/sampler/SamplerIS.cpp:49-87) in batches: draw from the prior, evaluate the
+ * likelihood (bcm3hip_eval_batch_device), keep every draw whose log-weight is within 23.02585 of the
+ * highest one seen so far, in draw order. */
+#define BCM3HIP_IS_MAX_D 1024
+/* The filter's state between batches, in device memory for bcm3hip_is_filter. Start from
+ * {-INFINITY, 0, -1, 0}. */
+typedef struct {
+    double run_max;   /* highest log-weight of the draws walked (the reference's heighest_weight) */
+    int64_t kept;     /* output rows filled */
+    int64_t consumed; /* global index of the last draw walked, -1 before the first; once kept == limit
+                         the index of the draw that filled the last row (draws walked = consumed + 1) */
+    int32_t nan_flag; /* a walked draw's log-likelihood was NaN: the run fails (Sampler.cpp:172-178) */
+    int32_t pad_;
+} bcm3hip_is_state;
+/* Draws g0 .. g0 + n - 1 of the prior (kinds and parameters as for bcm3hip_ptmh_propose_adaptive, d
+ * <= BCM3HIP_IS_MAX_D) into values[n][d] and their log prior density into lprior[n]. Draw g is the
+ * stream (seed, iteration g, chain 0): the draw bcm3hip_ptmh_propose_adaptive makes for a T = 0 chain
+ * with global index 0 at iteration g, bit for bit, whatever n, g0 and the launch shape. */
+int bcm3hip_is_draw(int64_t n, int d, const int32_t* prior_kind, const double* prior_p0, const double* prior_p1,
+                    const double* prior_p2, uint64_t g0, uint64_t seed, double* values, double* lprior, void* stream);
+/* The next n draws (llh[n], values[n][d], lprior[n]) through the filter: with lw = llh * learning_rate
+ * and M_j = max(run_max, lw_0 .. lw_j), draw j is dropped iff lw < M_j - 23.02585 (dropped draws raise
+ * the maximum too; the comparisons are the reference's, so -inf draws before the first finite one are
+ * kept with weight 0). Kept draws go to the output rows kept, kept + 1, ... in draw order: values, log
+ * prior, lw and the weight exp(lw), unnormalised. The walk ends with the draw that fills row limit - 1;
+ * later draws and later calls change nothing. A pure function of the log-weight sequence: any split
+ * into batches gives the same output and state. */
+int bcm3hip_is_filter(int64_t n, int d, const double* llh, const double* values, const double* lprior,
+                      double learning_rate, int64_t limit, bcm3hip_is_state* state, double* out_values,
+                      double* out_lprior, double* out_llh, double* out_weight, void* stream);
+/* The same rule as a sequential loop over host arrays (state in host memory); needs no device. */
+int bcm3hip_is_filter_host(int64_t n, int d, const double* llh, const double* values, const double* lprior,
+                           double learning_rate, int64_t limit, bcm3hip_is_state* state, double* out_values,
+                           double* out_lprior, double* out_llh, double* out_weight);
+
 #ifdef __cplusplus
 }
 #endif
