@@ -17,6 +17,7 @@
 #include "../../include/bcm3hip.h"
 #include "libm_exact.h"
 #include "ccm_kernel.h"
+#include "dev_buf.h"
 #include "incucyte_kernel.h"
 #include "popk_kernel.h"
 
@@ -42,25 +43,14 @@ size_t cp_assign_ws_bytes(int n);
 inline bool cp_assign_lds_fits(int n) { return cp_assign_ws_bytes(n) <= 52 * 1024; }
 }  // namespace bcm3hip
 
+// what a context evaluates; fixed at open
+enum class Kind { None, PopK, Analytic, ExpmPK, CellPop, Incucyte, Ccm };
+
+// Common state, then one block per kind. Every device buffer is a DevBuf (dev_buf.h) and is freed
+// with the context; the scratch grows in steps of at least kFloor elements and never shrinks.
 struct bcm3hip_ctx {
     int device = 0;
-    int kind = 0;  // 1 popk, 2 analytic, 3 expm pk, 4 cell population, 5 incucyte population, 6 cell cycle marker
-    CcmDevModel cm{};
-    bool ccm_one_lane = false;  // BCM3HIP_OPT_CCM_ONE_LANE
-    IncucyteDevModel im{};
-    // incucyte scratch, grow-only: simulated wells, CTB, per-well step counts / return codes /
-    // counters, and the step history of one chunk of items
-    double *inc_wells = nullptr, *inc_ctb = nullptr, *inc_history = nullptr;
-    int32_t *inc_steps = nullptr, *inc_codes = nullptr;
-    bcm3hip_traj_stats* inc_stats = nullptr;
-    bool inc_want_stats = false;  // the next launch also keeps each well's solver counters
-    size_t cap_inc_wells = 0, cap_inc_ctb = 0, cap_inc_history = 0, cap_inc_steps = 0, cap_inc_codes = 0,
-           cap_inc_stats = 0;
-    bcm3hip::CellPopDev* cp = nullptr;
-    std::vector<bcm3hip::CellPopDev*> cp_more;  // experiments 1.. of a cell-population likelihood
-    double* cp_logp = nullptr;                  // their per-experiment logp / status
-    int32_t *cp_status = nullptr, *cp_status0 = nullptr;
-    size_t cap_cp = 0, cap_cp_status = 0, cap_cp_status0 = 0;
+    Kind kind = Kind::None;
     int d = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -70,77 +60,60 @@ struct bcm3hip_ctx {
     bool log_timing = false;
     std::vector<hipEvent_t> log_ev;
     size_t log_used = 0;
-    PopPKDevModel pm{};
-    AnalyticDevModel am{};
-    ExpmPKDevModel xm{};
-    std::vector<void*> model_allocs;
-    // grow-only scratch
-    double* values = nullptr;
-    size_t cap_values = 0;
-    double* logp = nullptr;
-    int32_t* status = nullptr;
-    size_t cap_n = 0;
-    double* pllh = nullptr;
-    int32_t* tstatus = nullptr;
-    size_t cap_traj = 0, cap_tstatus = 0, cap_status = 0;
-    double* traj = nullptr;
-    size_t cap_trajout = 0;
-    double* exps = nullptr;  // expm pk: [n][n_jobs][n*n]
-    size_t cap_exps = 0;
-    bcm3hip_traj_stats* stats = nullptr;
-    size_t cap_stats = 0;
-    // the grow-only scratch above is shared by every launch of the context: a launch on another
+    ModelArrays model;  // the device copy of the model data
+    // staging of the host-pointer entry points
+    DevBuf<double> values, logp;
+    DevBuf<int32_t> status;
+    // the scratch of the blocks below is shared by every launch of the context: a launch on another
     // stream than the previous one waits for that one (scratch_ev), so concurrent callers on
     // different streams cannot overwrite each other's exponentials / per-patient results
     hipEvent_t scratch_ev = nullptr;
     hipStream_t scratch_stream = nullptr;
     bool scratch_used = false;
-    int lanes_per_wave = 0;  // 0 = auto (auto_lanes_per_wave)
-    int uni_solver = 0;      // BCM3HIP_OPT_UNI_SOLVER
-    int block_waves = 1;
-    int block_lds = 0;  // BCM3HIP_OPT_BLOCK_LDS
-    bool place_log = false;  // BCM3HIP_OPT_PLACEMENT_LOG
-    uint64_t* place = nullptr;
-    size_t cap_place = 0;
-    int64_t place_n = 0;
-    hipStream_t place_stream = nullptr;
+
+    struct {
+        PopPKDevModel m{};
+        DevBuf<double> pllh, traj;  // per-trajectory likelihoods; trajectories of a detail call
+        DevBuf<int32_t> tstatus;
+        DevBuf<bcm3hip_traj_stats> stats;
+        int lanes_per_wave = 0;  // 0 = auto (auto_lanes_per_wave)
+        int uni_solver = 0;      // BCM3HIP_OPT_UNI_SOLVER
+        int block_waves = 1;
+        int block_lds = 0;       // BCM3HIP_OPT_BLOCK_LDS
+        bool place_log = false;  // BCM3HIP_OPT_PLACEMENT_LOG
+        DevBuf<uint64_t> place;
+        int64_t place_n = 0;
+        hipStream_t place_stream = nullptr;
+    } popk;
+    AnalyticDevModel am{};
+    struct {
+        ExpmPKDevModel m{};
+        DevBuf<double> exps;  // [n][n_jobs][n*n]
+    } expm;
+    struct {
+        bcm3hip::CellPopDev* first = nullptr;
+        std::vector<bcm3hip::CellPopDev*> more;  // experiments 1.. of a cell-population likelihood
+        DevBuf<double> logp;                     // their per-experiment logp / status
+        DevBuf<int32_t> status, status0;
+    } cp;
+    struct {
+        IncucyteDevModel m{};
+        // simulated wells, CTB, per-well step counts / return codes / counters, and the step history
+        // of one chunk of items
+        DevBuf<double> wells, ctb, history;
+        DevBuf<int32_t> steps, codes;
+        DevBuf<bcm3hip_traj_stats> stats;
+        bool want_stats = false;  // the next launch also keeps each well's solver counters
+    } inc;
+    struct {
+        CcmDevModel m{};
+        bool one_lane = false;  // BCM3HIP_OPT_CCM_ONE_LANE
+    } ccm;
 };
 
-#define HIPCHK(x)                                                                                          \
-    do {                                                                                                   \
-        hipError_t e_ = (x);                                                                               \
-        if (e_ != hipSuccess) {                                                                            \
-            fprintf(stderr, "bcm3hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return BCM3HIP_ERR_HIP;                                                                        \
-        }                                                                                                  \
-    } while (0)
+static const size_t kFloor = 256;
 
-template <class T>
-static int grow(T*& p, size_t& cap, size_t need)
-{
-    if (need <= cap) return 0;
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t n = need < 256 ? 256 : need;
-    if (hipMalloc((void**)&p, n * sizeof(T)) != hipSuccess) return BCM3HIP_ERR_ALLOC;
-    cap = n;
-    return 0;
-}
-
-template <class T>
-static int upload(bcm3hip_ctx* c, const T* host, size_t count, const T** dev_out)
-{
-    *dev_out = nullptr;
-    if (count == 0) return 0;
-    if (!host) return BCM3HIP_ERR_ARG;
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, count * sizeof(T)));
-    c->model_allocs.push_back(p);
-    HIPCHK(hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice));
-    *dev_out = (const T*)p;
-    return 0;
-}
+#define HIPCHK(x) HIPCHK_AS("bcm3hip", x)
 
 static int ctx_common_init(bcm3hip_ctx* c, int device)
 {
@@ -236,9 +209,10 @@ int bcm3hip_open_popk(int device, const bcm3hip_popk_model* m, bcm3hip_ctx** out
         bcm3hip_close(c);
         return BCM3HIP_ERR_HIP;
     }
-    c->kind = 1;
+    c->kind = Kind::PopK;
     c->d = m->d;
-    PopPKDevModel& pm = c->pm;
+    PopPKDevModel& pm = c->popk.m;
+    ModelArrays& ma = c->model;
     pm.pk_type = m->pk_type;
     pm.N = m->N;
     pm.num_pk_params = m->num_pk_params;
@@ -261,14 +235,14 @@ int bcm3hip_open_popk(int device, const bcm3hip_popk_model* m, bcm3hip_ctx** out
     pm.fixed_kb = m->fixed_kb;
     pm.unity = 1.0;
     const size_t P = m->P, T = m->T;
-    if ((r = upload(c, m->transforms, (size_t)m->d, &pm.transforms)) ||
-        (r = upload(c, m->time, T, &pm.time)) || (r = upload(c, m->observed, P * T, &pm.observed)) ||
-        (r = upload(c, m->dose, P, &pm.dose)) || (r = upload(c, m->dosing_interval, P, &pm.dosing_interval)) ||
-        (r = upload(c, m->dose_after_dose_change, P, &pm.dose_after_dose_change)) ||
-        (r = upload(c, m->dose_change_time, P, &pm.dose_change_time)) ||
-        (r = upload(c, m->intermittent, P, &pm.intermittent)) ||
-        (r = upload(c, m->skipped_days, P * 29, &pm.skipped_days)) ||
-        (r = upload(c, m->simulate_until, P, &pm.simulate_until))) {
+    if ((r = ma.upload(m->transforms, (size_t)m->d, &pm.transforms)) ||
+        (r = ma.upload(m->time, T, &pm.time)) || (r = ma.upload(m->observed, P * T, &pm.observed)) ||
+        (r = ma.upload(m->dose, P, &pm.dose)) || (r = ma.upload(m->dosing_interval, P, &pm.dosing_interval)) ||
+        (r = ma.upload(m->dose_after_dose_change, P, &pm.dose_after_dose_change)) ||
+        (r = ma.upload(m->dose_change_time, P, &pm.dose_change_time)) ||
+        (r = ma.upload(m->intermittent, P, &pm.intermittent)) ||
+        (r = ma.upload(m->skipped_days, P * 29, &pm.skipped_days)) ||
+        (r = ma.upload(m->simulate_until, P, &pm.simulate_until))) {
         bcm3hip_close(c);
         return r;
     }
@@ -290,7 +264,7 @@ int bcm3hip_open_analytic(int device, const bcm3hip_analytic_model* m, bcm3hip_c
         bcm3hip_close(c);
         return r;
     }
-    c->kind = 2;
+    c->kind = Kind::Analytic;
     c->d = m->d;
     c->am.kind = m->kind;
     c->am.d = m->d;
@@ -363,14 +337,14 @@ int bcm3hip_open_mixture(int device, const bcm3hip_mixture_model* m, bcm3hip_ctx
     bcm3hip_ctx* c = new (std::nothrow) bcm3hip_ctx();
     if (!c) return BCM3HIP_ERR_ALLOC;
     int r = ctx_common_init(c, device);
-    if (r == 0) r = upload(c, m->means, (size_t)K * d, &c->am.mean);
-    if (r == 0) r = upload(c, (const double*)chol.data(), chol.size(), &c->am.chol);
-    if (r == 0) r = upload(c, (const double*)cst.data(), cst.size(), &c->am.cst);
+    if (r == 0) r = c->model.upload(m->means, (size_t)K * d, &c->am.mean);
+    if (r == 0) r = c->model.upload((const double*)chol.data(), chol.size(), &c->am.chol);
+    if (r == 0) r = c->model.upload((const double*)cst.data(), cst.size(), &c->am.cst);
     if (r) {
         bcm3hip_close(c);
         return r;
     }
-    c->kind = 2;
+    c->kind = Kind::Analytic;
     c->d = d;
     c->am.kind = bcm3hip::kAnalyticMixtureBase + m->kind;
     c->am.d = d;
@@ -388,17 +362,17 @@ int bcm3hip_open_cellpop_experiments(int device, const bcm3hip_cellpop_model* m,
     bcm3hip_ctx* c = new (std::nothrow) bcm3hip_ctx();
     if (!c) return BCM3HIP_ERR_ALLOC;
     int r = ctx_common_init(c, device);
-    if (r == 0) r = bcm3hip::cellpop_create(device, &m[0], &c->cp);
+    if (r == 0) r = bcm3hip::cellpop_create(device, &m[0], &c->cp.first);
     for (int k = 1; k < n_experiments && r == 0; k++) {
         bcm3hip::CellPopDev* e = nullptr;
         r = bcm3hip::cellpop_create(device, &m[k], &e);
-        if (r == 0) c->cp_more.push_back(e);
+        if (r == 0) c->cp.more.push_back(e);
     }
     if (r) {
         bcm3hip_close(c);
         return r;
     }
-    c->kind = 4;
+    c->kind = Kind::CellPop;
     c->d = m[0].d;
     *out = c;
     return 0;
@@ -414,11 +388,11 @@ int bcm3hip_cellpop_precompile(const bcm3hip_cellpop_model* m) { return bcm3hip:
 int bcm3hip_cellpop_cells(bcm3hip_ctx* c, size_t item, int32_t* count, bcm3hip_cell_record* records, double* values,
                           double* end_y)
 {
-    if (!c || c->kind != 4 || !count) return BCM3HIP_ERR_ARG;
+    if (!c || c->kind != Kind::CellPop || !count) return BCM3HIP_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipDeviceSynchronize());
-    return bcm3hip::cellpop_cells(c->cp, item, count, records, values, end_y);
+    return bcm3hip::cellpop_cells(c->cp.first, item, count, records, values, end_y);
 }
 
 int bcm3hip_open_expm_pk(int device, const bcm3hip_expm_pk_model* m, bcm3hip_ctx** out)
@@ -480,9 +454,10 @@ int bcm3hip_open_expm_pk(int device, const bcm3hip_expm_pk_model* m, bcm3hip_ctx
         bcm3hip_close(c);
         return BCM3HIP_ERR_HIP;
     }
-    c->kind = 3;
+    c->kind = Kind::ExpmPK;
     c->d = m->d;
-    ExpmPKDevModel& x = c->xm;
+    ExpmPKDevModel& x = c->expm.m;
+    ModelArrays& ma = c->model;
     x.d = m->d;
     x.n = n;
     x.n_transit = m->n_transit;
@@ -537,18 +512,18 @@ int bcm3hip_open_expm_pk(int device, const bcm3hip_expm_pk_model* m, bcm3hip_ctx
         }
     }
     x.n_jobs = (int32_t)job_dt.size();
-    if ((r = upload(c, job_dt.data(), job_dt.size(), &x.job_dt)) ||
-        (r = upload(c, job_patient.data(), job_patient.size(), &x.job_patient)) ||
-        (r = upload(c, interval_job.data(), interval_job.size(), &x.interval_job)) ||
-        (r = upload(c, obs_job.data(), obs_job.size(), &x.obs_job)) ||
-        (r = upload(c, pix.data(), pix.size(), &x.patient_ix)) ||
-        (r = upload(c, toff.data(), toff.size(), &x.treat_offset)) ||
-        (r = upload(c, ooff.data(), ooff.size(), &x.obs_offset)) ||
-        (r = upload(c, m->transforms, (size_t)m->d, &x.transforms)) ||
-        (r = upload(c, m->treat_times, (size_t)m->n_treat, &x.treat_times)) ||
-        (r = upload(c, m->treat_doses, (size_t)m->n_treat, &x.treat_doses)) ||
-        (r = upload(c, m->obs_times, (size_t)m->n_obs, &x.obs_times)) ||
-        (r = upload(c, m->obs_conc, (size_t)m->n_obs, &x.obs_conc))) {
+    if ((r = ma.upload(job_dt.data(), job_dt.size(), &x.job_dt)) ||
+        (r = ma.upload(job_patient.data(), job_patient.size(), &x.job_patient)) ||
+        (r = ma.upload(interval_job.data(), interval_job.size(), &x.interval_job)) ||
+        (r = ma.upload(obs_job.data(), obs_job.size(), &x.obs_job)) ||
+        (r = ma.upload(pix.data(), pix.size(), &x.patient_ix)) ||
+        (r = ma.upload(toff.data(), toff.size(), &x.treat_offset)) ||
+        (r = ma.upload(ooff.data(), ooff.size(), &x.obs_offset)) ||
+        (r = ma.upload(m->transforms, (size_t)m->d, &x.transforms)) ||
+        (r = ma.upload(m->treat_times, (size_t)m->n_treat, &x.treat_times)) ||
+        (r = ma.upload(m->treat_doses, (size_t)m->n_treat, &x.treat_doses)) ||
+        (r = ma.upload(m->obs_times, (size_t)m->n_obs, &x.obs_times)) ||
+        (r = ma.upload(m->obs_conc, (size_t)m->n_obs, &x.obs_conc))) {
         bcm3hip_close(c);
         return r;
     }
@@ -623,23 +598,23 @@ int bcm3hip_open_incucyte(int device, const bcm3hip_incucyte_model* m, bcm3hip_c
     if (!c) return BCM3HIP_ERR_ALLOC;
     int r = ctx_common_init(c, device);
     if (r == 0 && incucyte_prepare_device() != hipSuccess) r = BCM3HIP_ERR_HIP;
-    IncucyteDevModel& im = c->im;
+    IncucyteDevModel& im = c->inc.m;
     im.d = m->d;
     im.E = m->E;
     im.Tmax = Tmax;
     im.rtol = 1e-6;  // SetTolerance(1e-6, 1e-2), LikelihoodIncucytePopulation.cpp:131
     im.atol = 1e-2;
     im.ix = m->variables;
-    if (r == 0) r = upload(c, (const IncucyteDevExperiment*)exps.data(), exps.size(), &im.exps);
-    if (r == 0) r = upload(c, (const double*)times.data(), times.size(), &im.times);
-    if (r == 0) r = upload(c, (const double*)oc.data(), oc.size(), &im.obs_confluence);
-    if (r == 0) r = upload(c, (const double*)om.data(), om.size(), &im.obs_marker);
-    if (r == 0) r = upload(c, (const double*)octb.data(), octb.size(), &im.obs_ctb);
+    if (r == 0) r = c->model.upload((const IncucyteDevExperiment*)exps.data(), exps.size(), &im.exps);
+    if (r == 0) r = c->model.upload((const double*)times.data(), times.size(), &im.times);
+    if (r == 0) r = c->model.upload((const double*)oc.data(), oc.size(), &im.obs_confluence);
+    if (r == 0) r = c->model.upload((const double*)om.data(), om.size(), &im.obs_marker);
+    if (r == 0) r = c->model.upload((const double*)octb.data(), octb.size(), &im.obs_ctb);
     if (r) {
         bcm3hip_close(c);
         return r;
     }
-    c->kind = 5;
+    c->kind = Kind::Incucyte;
     c->d = m->d;
     *out = c;
     return 0;
@@ -654,14 +629,14 @@ int bcm3hip_open_cell_cycle_marker(int device, const bcm3hip_ccm_model* m, bcm3h
     bcm3hip_ctx* c = new (std::nothrow) bcm3hip_ctx();
     if (!c) return BCM3HIP_ERR_ALLOC;
     int r = ctx_common_init(c, device);
-    if (r == 0) r = upload(c, m->data, (size_t)m->T, &c->cm.data);
+    if (r == 0) r = c->model.upload(m->data, (size_t)m->T, &c->ccm.m.data);
     if (r) {
         bcm3hip_close(c);
         return r;
     }
-    c->kind = 6;
+    c->kind = Kind::Ccm;
     c->d = BCM3HIP_CCM_NVARS;
-    c->cm.T = m->T;
+    c->ccm.m.T = m->T;
     *out = c;
     return 0;
 }
@@ -669,28 +644,11 @@ int bcm3hip_open_cell_cycle_marker(int device, const bcm3hip_ccm_model* m, bcm3h
 int bcm3hip_close(bcm3hip_ctx* c)
 {
     if (!c) return 0;
+    // the context's device first: everything below, and every buffer the members own (freed by
+    // `delete`), goes back to the device it came from
     if (c->stream) hipSetDevice(c->device);
-    hipFree(c->inc_wells);
-    hipFree(c->inc_ctb);
-    hipFree(c->inc_history);
-    hipFree(c->inc_steps);
-    hipFree(c->inc_codes);
-    hipFree(c->inc_stats);
-    if (c->cp) bcm3hip::cellpop_destroy(c->cp);
-    for (auto* e : c->cp_more) bcm3hip::cellpop_destroy(e);
-    hipFree(c->cp_logp);
-    hipFree(c->cp_status);
-    hipFree(c->cp_status0);
-    for (void* p : c->model_allocs) hipFree(p);
-    hipFree(c->values);
-    hipFree(c->logp);
-    hipFree(c->status);
-    hipFree(c->pllh);
-    hipFree(c->exps);
-    hipFree(c->tstatus);
-    hipFree(c->traj);
-    hipFree(c->stats);
-    hipFree(c->place);
+    if (c->cp.first) bcm3hip::cellpop_destroy(c->cp.first);
+    for (auto* e : c->cp.more) bcm3hip::cellpop_destroy(e);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     if (c->scratch_ev) hipEventDestroy(c->scratch_ev);
@@ -706,11 +664,11 @@ int bcm3hip_set_option(bcm3hip_ctx* c, int option, int64_t value)
     switch (option) {
     case BCM3HIP_OPT_LANES_PER_WAVE:
         if (value < 0 || value > 64) return BCM3HIP_ERR_ARG;
-        c->lanes_per_wave = (int)value;
+        c->popk.lanes_per_wave = (int)value;
         return 0;
     case BCM3HIP_OPT_BLOCK_WAVES:
         if (value < 1 || value > 4) return BCM3HIP_ERR_ARG;
-        c->block_waves = (int)value;
+        c->popk.block_waves = (int)value;
         return 0;
     case BCM3HIP_OPT_TIMING_LOG:
         if (value != 0 && value != 1) return BCM3HIP_ERR_ARG;
@@ -719,19 +677,19 @@ int bcm3hip_set_option(bcm3hip_ctx* c, int option, int64_t value)
         return 0;
     case BCM3HIP_OPT_UNI_SOLVER:
         if (value != 0 && value != 1) return BCM3HIP_ERR_ARG;
-        c->uni_solver = (int)value;
+        c->popk.uni_solver = (int)value;
         return 0;
     case BCM3HIP_OPT_BLOCK_LDS:
         if (value < 0 || value > 65536) return BCM3HIP_ERR_ARG;
-        c->block_lds = (int)value;
+        c->popk.block_lds = (int)value;
         return 0;
     case BCM3HIP_OPT_PLACEMENT_LOG:
         if (value != 0 && value != 1) return BCM3HIP_ERR_ARG;
-        c->place_log = value != 0;
+        c->popk.place_log = value != 0;
         return 0;
     case BCM3HIP_OPT_CCM_ONE_LANE:
-        if (c->kind != 6 || (value != 0 && value != 1)) return BCM3HIP_ERR_ARG;
-        c->ccm_one_lane = value != 0;
+        if (c->kind != Kind::Ccm || (value != 0 && value != 1)) return BCM3HIP_ERR_ARG;
+        c->ccm.one_lane = value != 0;
         return 0;
     default: return BCM3HIP_ERR_ARG;
     }
@@ -742,11 +700,11 @@ int bcm3hip_num_variables(const bcm3hip_ctx* c) { return c ? c->d : -1; }
 int64_t bcm3hip_placement_log(bcm3hip_ctx* c, int64_t n_max, uint64_t* host_out)
 {
     if (!c || n_max < 0 || (n_max > 0 && !host_out)) return BCM3HIP_ERR_ARG;
-    if (!c->place || c->place_n == 0) return 0;
+    if (!c->popk.place || c->popk.place_n == 0) return 0;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->place_stream));
-    const int64_t m = n_max < c->place_n ? n_max : c->place_n;
-    if (m > 0) HIPCHK(hipMemcpy(host_out, c->place, (size_t)m * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipStreamSynchronize(c->popk.place_stream));
+    const int64_t m = n_max < c->popk.place_n ? n_max : c->popk.place_n;
+    if (m > 0) HIPCHK(hipMemcpy(host_out, c->popk.place, (size_t)m * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return m;
 }
 
@@ -758,26 +716,18 @@ int bcm3hip_assign_cells(int32_t n_problems, int32_t R, int32_t nsim, const doub
     if (n_problems == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int nw = R > nsim ? R : nsim;
-    unsigned char* ws = nullptr;
+    DevBuf<unsigned char> ws;  // this call's own, released once the stream is done with it
     size_t stride = 0;
     if (!bcm3hip::cp_assign_lds_fits(nw)) {
         stride = (bcm3hip::cp_assign_ws_bytes(nw) + 255) / 256 * 256;
-        HIPCHK(hipMalloc((void**)&ws, stride * n_problems));
+        if (ws.grow(stride * n_problems)) {
+            fprintf(stderr, "bcm3hip: the matching workspace (%zu bytes) could not be allocated\n", stride * n_problems);
+            return BCM3HIP_ERR_HIP;
+        }
     }
     hipError_t e = bcm3hip::launch_cp_assign(n_problems, R, nsim, lik, ws, stride, match, sum, ok, s);
-    if (ws) {
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        hipFree(ws);
-    }
+    if (ws && e == hipSuccess) e = hipStreamSynchronize(s);
     HIPCHK(e);
-    return 0;
-}
-
-static int ensure_traj_scratch(bcm3hip_ctx* c, size_t n)
-{
-    size_t ntraj = n * (size_t)c->pm.P;
-    if (grow(c->pllh, c->cap_traj, ntraj)) return BCM3HIP_ERR_ALLOC;
-    if (grow(c->tstatus, c->cap_tstatus, ntraj)) return BCM3HIP_ERR_ALLOC;
     return 0;
 }
 
@@ -800,21 +750,23 @@ static int launch_incucyte_ctx(bcm3hip_ctx* c, size_t n, const double* dvalues, 
                                bool want_stats, hipStream_t s, hipEvent_t e0, hipEvent_t e1, const int32_t* n_dev,
                                hipError_t* e)
 {
-    const IncucyteDevModel& im = c->im;
+    const IncucyteDevModel& im = c->inc.m;
     const size_t wells_per_item = (size_t)im.E * INC_WELLS;
     const size_t hist_per_item = wells_per_item * INC_HISTORY * 2;  // doubles
     const size_t chunk = std::min(n, std::max<size_t>(1, kIncucyteHistoryBytes / (hist_per_item * sizeof(double))));
-    if (grow(c->inc_wells, c->cap_inc_wells, n * (size_t)im.E * INC_ARRAYS * (size_t)im.Tmax * INC_WELLS) ||
-        grow(c->inc_ctb, c->cap_inc_ctb, n * (size_t)im.E * INC_CONC) ||
-        grow(c->inc_steps, c->cap_inc_steps, n * wells_per_item) ||
-        grow(c->inc_codes, c->cap_inc_codes, n * wells_per_item) ||
-        grow(c->inc_history, c->cap_inc_history, chunk * hist_per_item) ||
-        (want_stats && grow(c->inc_stats, c->cap_inc_stats, n * wells_per_item)))
+    auto& b = c->inc;
+    if (b.wells.grow(n * (size_t)im.E * INC_ARRAYS * (size_t)im.Tmax * INC_WELLS, kFloor) ||
+        b.ctb.grow(n * (size_t)im.E * INC_CONC, kFloor) || b.steps.grow(n * wells_per_item, kFloor) ||
+        b.codes.grow(n * wells_per_item, kFloor) || b.history.grow(chunk * hist_per_item, kFloor) ||
+        (want_stats && b.stats.grow(n * wells_per_item, kFloor)))
         return BCM3HIP_ERR_ALLOC;
-    *e = launch_incucyte(im, (int64_t)n, dvalues, dlogp, dstatus, c->inc_wells, c->inc_ctb, c->inc_steps, c->inc_codes,
-                         c->inc_history, want_stats ? c->inc_stats : nullptr, (int64_t)chunk, s, e0, e1, n_dev);
+    *e = launch_incucyte(im, (int64_t)n, dvalues, dlogp, dstatus, b.wells, b.ctb, b.steps, b.codes, b.history,
+                         want_stats ? b.stats.data() : nullptr, (int64_t)chunk, s, e0, e1, n_dev);
     return 0;
 }
+
+// the launches that take their evaluation count from device memory (n_dev): PopPK and incucyte
+static bool takes_device_count(const bcm3hip_ctx* c) { return c->kind == Kind::PopK || c->kind == Kind::Incucyte; }
 
 // scratch of the matrix-exponential path per launch: exps[n][n_jobs][n^2]; larger batches run in
 // chunks of evaluations so that it stays under this many bytes
@@ -824,8 +776,8 @@ static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp
                   double* dtraj, bcm3hip_traj_stats* dstats, hipStream_t s, const int32_t* n_dev = nullptr,
                   int32_t* dsteps = nullptr)
 {
-    if ((n_dev || dsteps) && c->kind != 1 && c->kind != 5) return BCM3HIP_ERR_ARG;  // PopPK / incucyte launches only
-    hipError_t e;
+    if ((n_dev || dsteps) && !takes_device_count(c)) return BCM3HIP_ERR_ARG;
+    hipError_t e = hipSuccess;
     if (c->scratch_used && c->scratch_stream != s) HIPCHK(hipStreamWaitEvent(s, c->scratch_ev, 0));
     hipEvent_t e0 = c->ev0, e1 = c->ev1;
     if (c->log_timing) {
@@ -840,56 +792,69 @@ static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp
         e1 = c->log_ev[2 * c->log_used + 1];
         c->log_used++;
     }
-    if (c->kind == 1) {
-        int r = ensure_traj_scratch(c, n);
-        if (r) return r;
+    switch (c->kind) {
+    case Kind::PopK: {
+        auto& b = c->popk;
+        const size_t ntraj = n * (size_t)b.m.P;
+        if (b.pllh.grow(ntraj, kFloor) || b.tstatus.grow(ntraj, kFloor)) return BCM3HIP_ERR_ALLOC;
         uint64_t* place = nullptr;
-        if (c->place_log) {
-            if (grow(c->place, c->cap_place, 4 * n * (size_t)c->pm.P)) return BCM3HIP_ERR_ALLOC;
-            HIPCHK(hipMemsetAsync(c->place, 0, 4 * n * (size_t)c->pm.P * sizeof(uint64_t), s));
-            place = c->place;
-            c->place_n = (int64_t)(n * (size_t)c->pm.P);
-            c->place_stream = s;
+        if (b.place_log) {
+            if (b.place.grow(4 * ntraj, kFloor)) return BCM3HIP_ERR_ALLOC;
+            HIPCHK(hipMemsetAsync(b.place, 0, 4 * ntraj * sizeof(uint64_t), s));
+            place = b.place;
+            b.place_n = (int64_t)ntraj;
+            b.place_stream = s;
         }
-        e = launch_popk(c->pm, (int64_t)n, dvalues, dlogp, dstatus, c->pllh, c->tstatus, dtraj, dstats,
-                        c->lanes_per_wave ? c->lanes_per_wave : auto_lanes_per_wave(n * (size_t)c->pm.P),
-                        c->block_waves, c->uni_solver, s, e0, e1, c->block_lds, n_dev, dsteps, place);
-    } else if (c->kind == 5) {
+        e = launch_popk(b.m, (int64_t)n, dvalues, dlogp, dstatus, b.pllh, b.tstatus, dtraj, dstats,
+                        b.lanes_per_wave ? b.lanes_per_wave : auto_lanes_per_wave(ntraj), b.block_waves, b.uni_solver, s,
+                        e0, e1, b.block_lds, n_dev, dsteps, place);
+        break;
+    }
+    case Kind::Incucyte: {
         if (n == 0) return 0;
-        int r = launch_incucyte_ctx(c, n, dvalues, dlogp, dstatus, c->inc_want_stats, s, e0, e1, n_dev, &e);
+        int r = launch_incucyte_ctx(c, n, dvalues, dlogp, dstatus, c->inc.want_stats, s, e0, e1, n_dev, &e);
         if (r) return r;
-    } else if (c->kind == 3) {
-        const size_t per_eval = (size_t)c->xm.n_jobs * (size_t)(c->xm.n * c->xm.n);
+        break;
+    }
+    case Kind::ExpmPK: {
+        const ExpmPKDevModel& x = c->expm.m;
+        const size_t per_eval = (size_t)x.n_jobs * (size_t)(x.n * x.n);
         const size_t chunk = per_eval == 0 ? n : std::max<size_t>(1, kExpmScratchBytes / (per_eval * sizeof(double)));
         const size_t nc = std::min(n, chunk);
-        if (grow(c->exps, c->cap_exps, std::max<size_t>(nc * per_eval, 1))) return BCM3HIP_ERR_ALLOC;
-        e = hipSuccess;
+        if (c->expm.exps.grow(std::max<size_t>(nc * per_eval, 1), kFloor)) return BCM3HIP_ERR_ALLOC;
         for (size_t i0 = 0; i0 < n && e == hipSuccess; i0 += nc) {
             const size_t m = std::min(nc, n - i0);
-            e = launch_expm_pk(c->xm, (int64_t)m, dvalues + i0 * (size_t)c->d, dlogp + i0, dstatus ? dstatus + i0 : nullptr,
-                               c->exps, s, i0 == 0 ? e0 : nullptr, i0 + m >= n ? e1 : nullptr);
+            e = launch_expm_pk(x, (int64_t)m, dvalues + i0 * (size_t)c->d, dlogp + i0, dstatus ? dstatus + i0 : nullptr,
+                               c->expm.exps, s, i0 == 0 ? e0 : nullptr, i0 + m >= n ? e1 : nullptr);
         }
-    } else if (c->kind == 4) {
+        break;
+    }
+    case Kind::CellPop: {
         // experiment 0 into logp, every further one into scratch, summed in experiment order
+        auto& b = c->cp;
         int32_t* st = dstatus;
-        if (!c->cp_more.empty()) {
-            if (!st && grow(c->cp_status0, c->cap_cp_status0, n)) return BCM3HIP_ERR_ALLOC;
-            if (!st) st = c->cp_status0;
-            if (grow(c->cp_logp, c->cap_cp, n) || grow(c->cp_status, c->cap_cp_status, n)) return BCM3HIP_ERR_ALLOC;
+        if (!b.more.empty()) {
+            if (!st && b.status0.grow(n, kFloor)) return BCM3HIP_ERR_ALLOC;
+            if (!st) st = b.status0;
+            if (b.logp.grow(n, kFloor) || b.status.grow(n, kFloor)) return BCM3HIP_ERR_ALLOC;
         }
-        int r = bcm3hip::cellpop_launch(c->cp, n, dvalues, dlogp, st, s, e0, c->cp_more.empty() ? e1 : nullptr);
+        int r = bcm3hip::cellpop_launch(b.first, n, dvalues, dlogp, st, s, e0, b.more.empty() ? e1 : nullptr);
         if (r) return r;
-        e = hipSuccess;
-        for (size_t k = 0; k < c->cp_more.size() && e == hipSuccess; k++) {
-            r = bcm3hip::cellpop_launch(c->cp_more[k], n, dvalues, c->cp_logp, c->cp_status, s, nullptr, nullptr);
+        for (size_t k = 0; k < b.more.size() && e == hipSuccess; k++) {
+            r = bcm3hip::cellpop_launch(b.more[k], n, dvalues, b.logp, b.status, s, nullptr, nullptr);
             if (r) return r;
-            e = bcm3hip::launch_cp_accumulate((int32_t)n, dlogp, st, c->cp_logp, c->cp_status, s);
+            e = bcm3hip::launch_cp_accumulate((int32_t)n, dlogp, st, b.logp, b.status, s);
         }
-        if (e == hipSuccess && e1 && !c->cp_more.empty()) e = hipEventRecord(e1, s);
-    } else if (c->kind == 6) {
-        e = launch_ccm(c->cm, (int64_t)n, dvalues, dlogp, dstatus, c->ccm_one_lane, s, e0, e1);
-    } else {
+        if (e == hipSuccess && e1 && !b.more.empty()) e = hipEventRecord(e1, s);
+        break;
+    }
+    case Kind::Ccm:
+        e = launch_ccm(c->ccm.m, (int64_t)n, dvalues, dlogp, dstatus, c->ccm.one_lane, s, e0, e1);
+        break;
+    case Kind::Analytic:
         e = launch_analytic(c->am, (int64_t)n, dvalues, dlogp, dstatus, s, e0, e1);
+        break;
+    default: return BCM3HIP_ERR_ARG;
     }
     if (e != hipSuccess) {
         fprintf(stderr, "bcm3hip: kernel launch failed: %s\n", hipGetErrorString(e));
@@ -906,33 +871,38 @@ static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp
 
 }  // extern "C"
 
+// room for a host batch's values / logp / status on the device, and the values copied in
+static int stage_batch(bcm3hip_ctx* c, size_t n, size_t d, const double* values)
+{
+    if (c->values.grow(n * d, kFloor) || c->logp.grow(n, kFloor) || c->status.grow(n, kFloor)) return BCM3HIP_ERR_ALLOC;
+    HIPCHK(hipMemcpyAsync(c->values, values, n * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
 static int incucyte_detail(bcm3hip_ctx* c, size_t n, size_t d, const double* values, double* logp, int32_t* status,
                            double* wells, double* ctb, int32_t* steps, int32_t* codes, bcm3hip_traj_stats* stats)
 {
     if ((int)d != c->d || (n > 0 && (!values || !logp))) return BCM3HIP_ERR_ARG;
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(c->device));
-    if (grow(c->values, c->cap_values, n * d)) return BCM3HIP_ERR_ALLOC;
-    if (grow(c->logp, c->cap_n, n)) return BCM3HIP_ERR_ALLOC;
-    if (grow(c->status, c->cap_status, n)) return BCM3HIP_ERR_ALLOC;
-    HIPCHK(hipMemcpyAsync(c->values, values, n * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    c->inc_want_stats = stats != nullptr;
-    int r = launch(c, n, c->values, c->logp, c->status, nullptr, nullptr, c->stream);
-    c->inc_want_stats = false;
+    int r = stage_batch(c, n, d, values);
     if (r) return r;
-    const size_t nw = n * (size_t)c->im.E * INC_WELLS;
+    auto& b = c->inc;
+    b.want_stats = stats != nullptr;
+    r = launch(c, n, c->values, c->logp, c->status, nullptr, nullptr, c->stream);
+    b.want_stats = false;
+    if (r) return r;
+    const size_t nw = n * (size_t)b.m.E * INC_WELLS;
     HIPCHK(hipMemcpyAsync(logp, c->logp, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (status) HIPCHK(hipMemcpyAsync(status, c->status, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (wells)
-        HIPCHK(hipMemcpyAsync(wells, c->inc_wells, nw * INC_ARRAYS * (size_t)c->im.Tmax * sizeof(double),
-                              hipMemcpyDeviceToHost, c->stream));
-    if (ctb)
-        HIPCHK(hipMemcpyAsync(ctb, c->inc_ctb, n * (size_t)c->im.E * INC_CONC * sizeof(double), hipMemcpyDeviceToHost,
+        HIPCHK(hipMemcpyAsync(wells, b.wells, nw * INC_ARRAYS * (size_t)b.m.Tmax * sizeof(double), hipMemcpyDeviceToHost,
                               c->stream));
-    if (steps) HIPCHK(hipMemcpyAsync(steps, c->inc_steps, nw * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (codes) HIPCHK(hipMemcpyAsync(codes, c->inc_codes, nw * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (stats)
-        HIPCHK(hipMemcpyAsync(stats, c->inc_stats, nw * sizeof(bcm3hip_traj_stats), hipMemcpyDeviceToHost, c->stream));
+    if (ctb)
+        HIPCHK(hipMemcpyAsync(ctb, b.ctb, n * (size_t)b.m.E * INC_CONC * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (steps) HIPCHK(hipMemcpyAsync(steps, b.steps, nw * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (codes) HIPCHK(hipMemcpyAsync(codes, b.codes, nw * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (stats) HIPCHK(hipMemcpyAsync(stats, b.stats, nw * sizeof(bcm3hip_traj_stats), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -952,7 +922,7 @@ int bcm3hip_eval_batch_device_counted(bcm3hip_ctx* c, size_t n_max, const int32_
                                       double* logp_dev, int32_t* status_dev, int32_t* steps_dev, void* stream)
 {
     if (!c || !n_dev || (n_max > 0 && (!values_dev || !logp_dev))) return BCM3HIP_ERR_ARG;
-    if (c->kind != 1 && c->kind != 5) return BCM3HIP_ERR_ARG;
+    if (!takes_device_count(c)) return BCM3HIP_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     return launch(c, n_max, values_dev, logp_dev, status_dev, nullptr, nullptr, (hipStream_t)stream, n_dev, steps_dev);
 }
@@ -989,33 +959,32 @@ int bcm3hip_eval_batch_detail(bcm3hip_ctx* c, size_t n, size_t d, const double* 
     if (!c || (int)d != c->d || (n > 0 && (!values || !logp))) return BCM3HIP_ERR_ARG;
     if (n == 0) return 0;
     // incucyte: ctb as patient_llh, the simulated wells as traj, each well's solver counters as stats
-    if (c->kind == 5) return incucyte_detail(c, n, d, values, logp, status, traj, patient_llh, nullptr, nullptr, stats);
-    if ((patient_llh || traj || stats) && c->kind != 1) return BCM3HIP_ERR_ARG;
+    if (c->kind == Kind::Incucyte)
+        return incucyte_detail(c, n, d, values, logp, status, traj, patient_llh, nullptr, nullptr, stats);
+    if ((patient_llh || traj || stats) && c->kind != Kind::PopK) return BCM3HIP_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    if (grow(c->values, c->cap_values, n * d)) return BCM3HIP_ERR_ALLOC;
-    if (grow(c->logp, c->cap_n, n)) return BCM3HIP_ERR_ALLOC;
-    if (grow(c->status, c->cap_status, n)) return BCM3HIP_ERR_ALLOC;
-    size_t ntraj = (c->kind == 1) ? n * (size_t)c->pm.P : 0;
+    auto& b = c->popk;
+    const size_t ntraj = (c->kind == Kind::PopK) ? n * (size_t)b.m.P : 0;
+    const size_t traj_len = (size_t)b.m.N * (size_t)b.m.T;
     double* dtraj = nullptr;
     bcm3hip_traj_stats* dstats = nullptr;
     if (traj) {
-        if (grow(c->traj, c->cap_trajout, ntraj * (size_t)c->pm.N * (size_t)c->pm.T)) return BCM3HIP_ERR_ALLOC;
-        dtraj = c->traj;
+        if (b.traj.grow(ntraj * traj_len, kFloor)) return BCM3HIP_ERR_ALLOC;
+        dtraj = b.traj;
     }
     if (stats) {
-        if (grow(c->stats, c->cap_stats, ntraj)) return BCM3HIP_ERR_ALLOC;
-        dstats = c->stats;
+        if (b.stats.grow(ntraj, kFloor)) return BCM3HIP_ERR_ALLOC;
+        dstats = b.stats;
     }
-    HIPCHK(hipMemcpyAsync(c->values, values, n * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    int r = launch(c, n, c->values, c->logp, c->status, dtraj, dstats, c->stream);
+    int r = stage_batch(c, n, d, values);
+    if (r == 0) r = launch(c, n, c->values, c->logp, c->status, dtraj, dstats, c->stream);
     if (r) return r;
     HIPCHK(hipMemcpyAsync(logp, c->logp, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (status) HIPCHK(hipMemcpyAsync(status, c->status, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (patient_llh)
-        HIPCHK(hipMemcpyAsync(patient_llh, c->pllh, ntraj * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(patient_llh, b.pllh, ntraj * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (traj)
-        HIPCHK(hipMemcpyAsync(traj, dtraj, ntraj * c->pm.N * c->pm.T * sizeof(double), hipMemcpyDeviceToHost,
-                              c->stream));
+        HIPCHK(hipMemcpyAsync(traj, dtraj, ntraj * traj_len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (stats)
         HIPCHK(hipMemcpyAsync(stats, dstats, ntraj * sizeof(bcm3hip_traj_stats), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1025,7 +994,7 @@ int bcm3hip_eval_batch_detail(bcm3hip_ctx* c, size_t n, size_t d, const double* 
 int bcm3hip_eval_batch_incucyte_detail(bcm3hip_ctx* c, size_t n, size_t d, const double* values, double* logp,
                                        int32_t* status, double* wells, double* ctb, int32_t* steps, int32_t* codes)
 {
-    if (!c || c->kind != 5) return BCM3HIP_ERR_ARG;
+    if (!c || c->kind != Kind::Incucyte) return BCM3HIP_ERR_ARG;
     return incucyte_detail(c, n, d, values, logp, status, wells, ctb, steps, codes, nullptr);
 }
 

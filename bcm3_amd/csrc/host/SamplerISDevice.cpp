@@ -6,21 +6,11 @@
 #include <limits>
 
 #include "../../../include/bcm3hip.h"
+#include "DevBuf.h"
 #include "NetCDFClassic.h"
 #include "log.h"
 
 namespace bcm3 {
-
-namespace {
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    bool alloc(size_t count) { return bcm3hip_malloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T)) == 0; }
-    ~DevBuf() { bcm3hip_free(p); }
-};
-
-}  // namespace
 
 struct SamplerISDevice::Impl {
     ISConfig cfg;

@@ -15,6 +15,7 @@
 
 #include "../../../include/bcm3.h"
 #include "../../../include/bcm3hip.h"
+#include "DevBuf.h"
 #include "GMM.h"
 #include "NetCDFClassic.h"
 #include "log.h"
@@ -196,37 +197,6 @@ std::unique_ptr<Transport> MakeLocalTransport(std::shared_ptr<LocalGroup> group,
     if (!group || rank < 0 || rank >= group->world) return nullptr;
     return std::unique_ptr<Transport>(new LocalTransport(std::move(group), rank));
 }
-
-// ---------------------------------------------------------------------------------------------
-// device buffers
-
-namespace {
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    bool alloc(size_t count)
-    {
-        n = count;
-        return bcm3hip_malloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T)) == 0;
-    }
-    ~DevBuf() { bcm3hip_free(p); }
-};
-
-template <class T>
-bool Upload(DevBuf<T>& b, const std::vector<T>& h, void* s)
-{
-    return bcm3hip_memcpy_async(b.p, h.data(), h.size() * sizeof(T), BCM3HIP_H2D, s) == 0;
-}
-template <class T>
-bool Download(std::vector<T>& h, const DevBuf<T>& b, void* s)
-{
-    h.resize(b.n);
-    return bcm3hip_memcpy_async(h.data(), b.p, b.n * sizeof(T), BCM3HIP_D2H, s) == 0 && bcm3hip_stream_synchronize(s) == 0;
-}
-
-}  // namespace
 
 struct SamplerPTDevice::Impl {
     PTMHConfig cfg;
