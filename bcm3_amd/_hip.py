@@ -148,6 +148,50 @@ def cell_cycle_marker_host(data, values) -> np.ndarray:
     return logp
 
 
+def popk_time(m: PopPKModel) -> np.ndarray:
+    """a copy of the output times [T] of a bcm3hip_popk_model"""
+    if not m.time or m.T <= 0:
+        return np.empty(0)
+    return np.ctypeslib.as_array(C.cast(m.time, C.POINTER(C.c_double)), shape=(int(m.T),)).copy()
+
+
+PREDICT_MAX_N = 8192      # BCM3HIP_PREDICT_MAX_N
+PREDICT_MAX_PROBS = 16    # BCM3HIP_PREDICT_MAX_PROBS
+
+
+def column_quantiles_host(data, probs):
+    """bcm3hip_column_quantiles_host: the quantile kernel's source compiled for the host -- per column
+    of data [n, cols] (NaN = no value) the type-7 quantiles q [n_probs, cols], the mean [cols] and the
+    count [cols] of non-NaN values. Needs no device."""
+    x = np.ascontiguousarray(data, dtype=np.float64)
+    n, cols = x.shape
+    p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    q = np.empty((p.size, cols))
+    mean = np.empty(cols)
+    count = np.empty(cols, dtype=np.int32)
+    check(lib().bcm3hip_column_quantiles_host(n, cols, x.ctypes.data, p.size, p.ctypes.data, q.ctypes.data,
+                                              mean.ctypes.data, count.ctypes.data), "bcm3hip_column_quantiles_host")
+    return q, mean, count
+
+
+def column_quantiles(data, probs):
+    """bcm3hip_column_quantiles on data's device and torch's current stream: data is a CUDA float64
+    tensor [n, cols]. Returns CUDA tensors (q [n_probs, cols], mean [cols], count [cols] int32); the
+    launch is asynchronous."""
+    import torch
+    x = data.contiguous()
+    n, cols = x.shape
+    p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    q = torch.empty((p.size, cols), dtype=torch.float64, device=x.device)
+    mean = torch.empty(cols, dtype=torch.float64, device=x.device)
+    count = torch.empty(cols, dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        check(lib().bcm3hip_column_quantiles(n, cols, x.data_ptr(), p.size, p.ctypes.data, q.data_ptr(),
+                                             mean.data_ptr(), count.data_ptr(), stream), "bcm3hip_column_quantiles")
+    return q, mean, count
+
+
 STATS_DTYPE = np.dtype([(k, np.int32) for k in ("nst", "nfe", "nni", "nsetups", "nje", "netf", "ncfn", "nreinit")])
 
 _lib = None
@@ -224,6 +268,14 @@ def lib() -> C.CDLL:
     L.bcm3hip_open_cell_cycle_marker.restype = C.c_int
     L.bcm3hip_cell_cycle_marker_host.argtypes = [C.POINTER(CcmModel), i64, vp, vp]
     L.bcm3hip_cell_cycle_marker_host.restype = C.c_int
+    L.bcm3hip_column_quantiles.argtypes = [i64, i64, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.bcm3hip_column_quantiles.restype = C.c_int
+    L.bcm3hip_column_quantiles_host.argtypes = [i64, i64, vp, C.c_int, vp, vp, vp, vp]
+    L.bcm3hip_column_quantiles_host.restype = C.c_int
+    L.bcm3hip_predict.argtypes = [vp, sz, sz, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.bcm3hip_predict.restype = C.c_int
+    L.bcm3hip_predict_last_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.bcm3hip_predict_last_ms.restype = C.c_int
     for f in ("bcm3hip_open_popk", "bcm3hip_open_analytic", "bcm3hip_open_mixture", "bcm3hip_open_expm_pk", "bcm3hip_close", "bcm3hip_set_option",
               "bcm3hip_num_variables", "bcm3hip_eval_batch", "bcm3hip_eval_batch_device",
               "bcm3hip_last_kernel_ms", "bcm3hip_eval_batch_detail"):
@@ -265,6 +317,7 @@ class Context:
     def __init__(self, handle, d: int, P: int = 1, N: int = 0, T: int = 0, keep=None):
         self.h = handle
         self.d, self.P, self.N, self.T = d, P, N, T
+        self.time = np.empty(0)  # PopPK contexts: the output times [T]
         self._keep = keep
 
     @classmethod
@@ -286,7 +339,9 @@ class Context:
                 setattr(m, name, v)
         h = C.c_void_p()
         check(lib().bcm3hip_open_popk(device, C.byref(m), C.byref(h)), "bcm3hip_open_popk")
-        return cls(h, int(m.d), int(m.P), int(m.N), int(m.T))
+        ctx = cls(h, int(m.d), int(m.P), int(m.N), int(m.T))
+        ctx.time = popk_time(m)
+        return ctx
 
     @classmethod
     def from_popk_model(cls, m: "PopPKModel", device: int = 0) -> "Context":
@@ -294,7 +349,9 @@ class Context:
         bcm3.Likelihood.popk_model(), whose arrays live as long as that likelihood)."""
         h = C.c_void_p()
         check(lib().bcm3hip_open_popk(device, C.byref(m), C.byref(h)), "bcm3hip_open_popk")
-        return cls(h, int(m.d), int(m.P), int(m.N), int(m.T))
+        ctx = cls(h, int(m.d), int(m.P), int(m.N), int(m.T))
+        ctx.time = popk_time(m)
+        return ctx
 
     @classmethod
     def analytic(cls, kind: int, d: int, p0: float, p1: float, p2: float = 0.0, device: int = 0) -> "Context":
@@ -370,6 +427,25 @@ class Context:
                                               _ptr(traj), _ptr(stats)), "eval_batch_detail")
         return dict(logp=logp, status=status, patient_llh=pllh.reshape(n, self.P),
                     traj=traj.reshape(n, self.P, self.N, self.T), stats=stats.reshape(n, self.P))
+
+    def predict(self, values: np.ndarray, probs):
+        """bcm3hip_predict (PopPK contexts): the bands of the trajectories values [n, d] simulate, reduced
+        on the device -- dict(quantiles [n_probs, P, N, T], mean and count [P, N, T], logp, status [n])."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        shape = (self.P, self.N, self.T)
+        out = dict(quantiles=np.empty((p.size,) + shape), mean=np.empty(shape), count=np.empty(shape, dtype=np.int32),
+                   logp=np.empty(n), status=np.empty(n, dtype=np.int32))
+        check(lib().bcm3hip_predict(self.h, n, self.d, _ptr(v), p.size, _ptr(p), *(_ptr(out[k]) for k in
+                                    ("quantiles", "mean", "count", "logp", "status"))), "bcm3hip_predict")
+        return out
+
+    def predict_last_ms(self):
+        """(quantile kernel ms, whole call ms) of the last predict, by HIP events on the context's stream"""
+        qms, tms = C.c_float(), C.c_float()
+        check(lib().bcm3hip_predict_last_ms(self.h, C.byref(qms), C.byref(tms)), "bcm3hip_predict_last_ms")
+        return float(qms.value), float(tms.value)
 
     def eval_device(self, n: int, values_ptr: int, logp_ptr: int, status_ptr: Optional[int] = None,
                     stream: Optional[int] = None):

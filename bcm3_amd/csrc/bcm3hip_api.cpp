@@ -20,6 +20,7 @@
 #include "dev_buf.h"
 #include "incucyte_kernel.h"
 #include "popk_kernel.h"
+#include "predict_quantile.h"
 
 const xm::GlibcPow* bcm3_pow_tables(int* from_libm);  // libm_tables.cpp
 
@@ -84,6 +85,12 @@ struct bcm3hip_ctx {
         DevBuf<uint64_t> place;
         int64_t place_n = 0;
         hipStream_t place_stream = nullptr;
+        // bcm3hip_predict: the bands of the trajectories in `traj`, and the event pairs around the
+        // quantile kernel and around the whole call (created by the first call)
+        DevBuf<double> pred_q, pred_mean;
+        DevBuf<int32_t> pred_count;
+        hipEvent_t pred_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        bool pred_timed = false;
     } popk;
     AnalyticDevModel am{};
     struct {
@@ -653,6 +660,8 @@ int bcm3hip_close(bcm3hip_ctx* c)
     if (c->ev1) hipEventDestroy(c->ev1);
     if (c->scratch_ev) hipEventDestroy(c->scratch_ev);
     for (hipEvent_t e : c->log_ev) hipEventDestroy(e);
+    for (hipEvent_t e : c->popk.pred_ev)
+        if (e) hipEventDestroy(e);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return 0;
@@ -988,6 +997,59 @@ int bcm3hip_eval_batch_detail(bcm3hip_ctx* c, size_t n, size_t d, const double* 
     if (stats)
         HIPCHK(hipMemcpyAsync(stats, dstats, ntraj * sizeof(bcm3hip_traj_stats), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int bcm3hip_predict(bcm3hip_ctx* c, size_t n, size_t d, const double* values, int n_probs, const double* probs,
+                    double* q, double* mean, int32_t* count, double* logp, int32_t* status)
+{
+    if (!c || c->kind != Kind::PopK || (int)d != c->d || !values || !probs || !q || !logp) return BCM3HIP_ERR_ARG;
+    if (n < 1 || n > (size_t)PREDICT_MAX_N || n_probs < 1 || n_probs > PREDICT_MAX_PROBS) return BCM3HIP_ERR_ARG;
+    PredictProbs pr{};
+    for (int k = 0; k < n_probs; k++) {
+        if (!(probs[k] >= 0.0 && probs[k] <= 1.0)) return BCM3HIP_ERR_ARG;
+        pr.p[k] = probs[k];
+    }
+    HIPCHK(hipSetDevice(c->device));
+    auto& b = c->popk;
+    const size_t cols = (size_t)b.m.P * (size_t)b.m.N * (size_t)b.m.T;  // traj[n][P][N][T] as data[n][cols]
+    if (b.traj.grow(n * cols, kFloor) || b.pred_q.grow((size_t)n_probs * cols, kFloor) ||
+        b.pred_mean.grow(cols, kFloor) || b.pred_count.grow(cols, kFloor))
+        return BCM3HIP_ERR_ALLOC;
+    for (hipEvent_t& e : b.pred_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    b.pred_timed = false;
+    HIPCHK(hipEventRecord(b.pred_ev[0], c->stream));
+    int r = stage_batch(c, n, d, values);
+    if (r == 0) r = launch(c, n, c->values, c->logp, c->status, b.traj, nullptr, c->stream);
+    if (r) return r;
+    HIPCHK(hipEventRecord(b.pred_ev[2], c->stream));
+    const hipError_t e = launch_predict_quantiles((int64_t)n, (int64_t)cols, b.traj, n_probs, pr, b.pred_q, b.pred_mean,
+                                                  b.pred_count, c->stream);
+    if (e != hipSuccess) {
+        fprintf(stderr, "bcm3hip: quantile kernel launch failed: %s\n", hipGetErrorString(e));
+        return BCM3HIP_ERR_HIP;
+    }
+    HIPCHK(hipEventRecord(b.pred_ev[3], c->stream));
+    HIPCHK(hipMemcpyAsync(logp, c->logp, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, c->status, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (cols) {
+        HIPCHK(hipMemcpyAsync(q, b.pred_q, (size_t)n_probs * cols * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (mean) HIPCHK(hipMemcpyAsync(mean, b.pred_mean, cols * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (count) HIPCHK(hipMemcpyAsync(count, b.pred_count, cols * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipEventRecord(b.pred_ev[1], c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    b.pred_timed = true;
+    return 0;
+}
+
+int bcm3hip_predict_last_ms(bcm3hip_ctx* c, float* quantile_ms, float* total_ms)
+{
+    if (!c || c->kind != Kind::PopK || !c->popk.pred_timed) return BCM3HIP_ERR_ARG;
+    auto& b = c->popk;
+    if (quantile_ms) HIPCHK(hipEventElapsedTime(quantile_ms, b.pred_ev[2], b.pred_ev[3]));
+    if (total_ms) HIPCHK(hipEventElapsedTime(total_ms, b.pred_ev[0], b.pred_ev[1]));
     return 0;
 }
 

@@ -148,6 +148,38 @@ int bcm3_likelihood_incucyte_detail(bcm3_likelihood* h, size_t n, const double* 
                                               steps, codes);
 }
 
+int bcm3_likelihood_predict_status(bcm3_likelihood* h, size_t n, const double* values, int n_probs,
+                                   const double* probs, double* q, double* mean, int32_t* count, double* logp,
+                                   int32_t* status)
+{
+    if (!h || !h->ll) return -1;
+    bcm3::LikelihoodGPUBase* p = dynamic_cast<bcm3::LikelihoodPopPKTrajectory*>(h->ll.get());
+    if (!p) p = dynamic_cast<bcm3::LikelihoodPharmacokineticTrajectory*>(h->ll.get());
+    if (!p) {
+        LOGERROR("posterior predictive bands need a likelihood with a trajectory output (pop_pk_trajectory or "
+                 "pharmacokinetic_trajectory)");
+        return -2;
+    }
+    if (!p->Context()) {
+        LOGERROR("posterior predictive bands need a device; the likelihood was created without one");
+        return -2;
+    }
+    const int r = bcm3hip_predict(p->Context(), n, p->GetNumVariables(), values, n_probs, probs, q, mean, count, logp,
+                                  status);
+    if (r) {
+        LOGERROR("bcm3hip_predict: %s (at most %d parameter vectors and %d probabilities in [0, 1] per call)",
+                 bcm3hip_error_string(r), BCM3HIP_PREDICT_MAX_N, BCM3HIP_PREDICT_MAX_PROBS);
+        return -3;
+    }
+    return 0;
+}
+
+int bcm3_likelihood_predict(bcm3_likelihood* h, size_t n, const double* values, int n_probs, const double* probs,
+                            double* q, double* mean, int32_t* count, double* logp)
+{
+    return bcm3_likelihood_predict_status(h, n, values, n_probs, probs, q, mean, count, logp, nullptr);
+}
+
 int64_t bcm3_likelihood_ccm_track(const bcm3_likelihood* h, double* data, int64_t cap, int32_t* track_ix)
 {
     if (!h || !h->ll) return -1;

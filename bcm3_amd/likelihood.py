@@ -33,6 +33,8 @@ def lib() -> C.CDLL:
     L.bcm3_likelihood_expm_pk_model.argtypes = [vp, C.POINTER(_hip.ExpmPKModel)]
     L.bcm3_likelihood_incucyte_model.argtypes = [vp, C.POINTER(_hip.IncucyteModel)]
     L.bcm3_likelihood_incucyte_detail.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.bcm3_likelihood_predict.argtypes = [vp, sz, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.bcm3_likelihood_predict_status.argtypes = [vp, sz, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.bcm3_likelihood_ccm_track.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int32)]
     L.bcm3_likelihood_ccm_track.restype = C.c_int64
     L.bcm3_table_read.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_int64), vp, C.c_int64]
@@ -160,6 +162,28 @@ class Likelihood:
                                                   ("logp", "status", "wells", "ctb", "steps", "codes")))
         if r != 0:
             _err("bcm3_likelihood_incucyte_detail", r)
+        return out
+
+    def predict(self, values, probs) -> dict:
+        """pop_pk_trajectory / pharmacokinetic_trajectory: the posterior predictive bands of values [n, d]
+        (bcm3_likelihood_predict_status; bcm3_amd.predict is the front end): quantiles [n_probs, P, N, T],
+        mean and count [P, N, T], logp and status [n], time [T]."""
+        try:
+            m = self.popk_model()
+        except RuntimeError:
+            m = None  # the library call below refuses the type with its own message
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        shape = (m.P, m.N, m.T) if m is not None else (0, 0, 0)
+        out = dict(quantiles=np.empty((p.size,) + shape), mean=np.empty(shape), count=np.empty(shape, dtype=np.int32),
+                   logp=np.empty(n), status=np.empty(n, dtype=np.int32))
+        r = lib().bcm3_likelihood_predict_status(self.h, n, v.ctypes.data, p.size, p.ctypes.data,
+                                                 *(out[k].ctypes.data for k in
+                                                   ("quantiles", "mean", "count", "logp", "status")))
+        if r != 0:
+            _err("bcm3_likelihood_predict", r)
+        out["time"] = _hip.popk_time(m)
         return out
 
     def ccm_track(self):

@@ -48,6 +48,20 @@ int bcm3_likelihood_incucyte_model(const bcm3_likelihood* ll, void* model);
 /* bcm3hip_eval_batch_incucyte_detail on the likelihood's context (-2: another type, or no device) */
 int bcm3_likelihood_incucyte_detail(bcm3_likelihood* ll, size_t n, const double* values, double* logp, int32_t* status,
                                     double* wells, double* ctb, int32_t* steps, int32_t* codes);
+/* Posterior predictive bands (bcm3hip_predict on the likelihood's context): the simulated
+ * trajectories of values[n][d] reduced on the device to q[n_probs][P][N][T] (type-7 quantiles at
+ * probs[n_probs], each in [0, 1]), mean[P][N][T] and count[P][N][T] (the draws that reached the time
+ * point; either may be NULL), with logp[n]; P patients, N states, T time points of
+ * bcm3_likelihood_popk_model. At most 8192 vectors and 16 probabilities per call. -2 when the
+ * likelihood type has no trajectory output (anything but pop_pk_trajectory and
+ * pharmacokinetic_trajectory) or the likelihood has no device, -3 when the device call fails; the
+ * message is in bcm3_last_error(). */
+int bcm3_likelihood_predict(bcm3_likelihood* ll, size_t n, const double* values, int n_probs, const double* probs,
+                            double* q, double* mean, int32_t* count, double* logp);
+/* the same with the evaluations' status[n] (BCM3HIP_STATUS_*; may be NULL) */
+int bcm3_likelihood_predict_status(bcm3_likelihood* ll, size_t n, const double* values, int n_probs,
+                                   const double* probs, double* q, double* mean, int32_t* count, double* logp,
+                                   int32_t* status);
 /* cell_cycle_marker: the track the likelihood evaluates against (the row ccm.track_ix selected):
  * copies up to cap frames into data (may be NULL) and the row index into *track_ix (may be NULL);
  * returns the number of frames, -2 for other likelihood types. */

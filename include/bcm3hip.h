@@ -871,6 +871,40 @@ int bcm3hip_nccl_exchange(void* comm, int n_send, const double* const* send, con
 int bcm3hip_eval_batch_detail(bcm3hip_ctx* ctx, size_t n, size_t d, const double* values, double* logp,
                               int32_t* status, double* patient_llh, double* traj, bcm3hip_traj_stats* stats);
 
+/* ---- Posterior predictive bands (predict_kernels.hip) ----
+ * Per column of a row-major data[n][cols] of doubles, NaN meaning "no value": count[col] = m, the
+ * number of non-NaN values; q[k][col] = the Hyndman-Fan type-7 quantile (R's default, numpy's
+ * "linear") of those m values at probability probs[k], computed on the values sorted ascending
+ * (-inf < ... < -0.0 < +0.0 < ... < +inf) as
+ *   h = (double)(m - 1) * p, lo = floor(h), g = h - lo,
+ *   q = x[lo] when g == 0, else x[lo] + g * (x[lo + 1] - x[lo]);
+ * mean[col] = their sum in ascending order, one term after the other, divided by m. A column without
+ * values gives NaN quantiles and mean.
+ * Limits: 1 <= n <= BCM3HIP_PREDICT_MAX_N (one workgroup sorts a column in 64 KB of LDS), 1 <=
+ * n_probs <= BCM3HIP_PREDICT_MAX_PROBS, every probability in [0, 1]; anything else is
+ * BCM3HIP_ERR_ARG before any launch. mean and count may be NULL. */
+#define BCM3HIP_PREDICT_MAX_N 8192
+#define BCM3HIP_PREDICT_MAX_PROBS 16
+/* On device buffers (probs on the host), on the current device, asynchronous on `stream`. */
+int bcm3hip_column_quantiles(int64_t n, int64_t cols, const double* data_dev, int n_probs, const double* probs_host,
+                             double* q_dev /*[n_probs][cols]*/, double* mean_dev /*[cols]*/,
+                             int32_t* count_dev /*[cols]*/, void* stream);
+/* The same source compiled for the host, host buffers throughout; needs no device. Bit-identical to
+ * the kernel. */
+int bcm3hip_column_quantiles_host(int64_t n, int64_t cols, const double* data, int n_probs, const double* probs,
+                                  double* q, double* mean, int32_t* count);
+/* The bands of n parameter vectors' simulated trajectories (PopPK contexts: pop_pk_trajectory and
+ * pharmacokinetic_trajectory; other kinds: BCM3HIP_ERR_ARG). Evaluates values[n][d] (host) as
+ * bcm3hip_eval_batch_detail does with traj requested, keeps traj[n][P][N][T] on the device, runs
+ * the quantile kernel on it as data[n][P*N*T] on the same stream and copies back only
+ * q[n_probs][P][N][T], mean[P][N][T], count[P][N][T] (either may be NULL), logp[n] and status[n]
+ * (may be NULL). Synchronous. */
+int bcm3hip_predict(bcm3hip_ctx* ctx, size_t n, size_t d, const double* values, int n_probs, const double* probs,
+                    double* q, double* mean, int32_t* count, double* logp, int32_t* status);
+/* HIP-event times of the last bcm3hip_predict of the context (either may be NULL): the quantile
+ * kernel alone, and the whole call from the upload of values to the last copy back. */
+int bcm3hip_predict_last_ms(bcm3hip_ctx* ctx, float* quantile_ms, float* total_ms);
+
 /* ---- Importance sampler (is_kernels.hip) ----
  * SamplerIS::RunImpl (src/sampler/SamplerIS.cpp:49-87) in batches: draw from the prior, evaluate the
  * likelihood (bcm3hip_eval_batch_device), keep every draw whose log-weight is within 23.02585 of the
