@@ -155,6 +155,13 @@ def popk_time(m: PopPKModel) -> np.ndarray:
     return np.ctypeslib.as_array(C.cast(m.time, C.POINTER(C.c_double)), shape=(int(m.T),)).copy()
 
 
+def popk_observed(m: PopPKModel) -> np.ndarray:
+    """a copy of the observations [P, T] of a bcm3hip_popk_model (NaN = not observed)"""
+    if not m.observed or m.T <= 0 or m.P <= 0:
+        return np.empty((0, 0))
+    return np.ctypeslib.as_array(C.cast(m.observed, C.POINTER(C.c_double)), shape=(int(m.P), int(m.T))).copy()
+
+
 PREDICT_MAX_N = 8192      # BCM3HIP_PREDICT_MAX_N
 PREDICT_MAX_PROBS = 16    # BCM3HIP_PREDICT_MAX_PROBS
 
@@ -190,6 +197,62 @@ def column_quantiles(data, probs):
         check(lib().bcm3hip_column_quantiles(n, cols, x.data_ptr(), p.size, p.ctypes.data, q.data_ptr(),
                                              mean.data_ptr(), count.data_ptr(), stream), "bcm3hip_column_quantiles")
     return q, mean, count
+
+
+def t4_draws_host(seed: int, n: int, P: int, T: int) -> np.ndarray:
+    """bcm3hip_t4_draws_host: tau [n, P, T], the Student-t(4) variates predict_obs scales and adds to
+    the concentrations; a function of (seed, row, patient, time index) alone. Needs no device."""
+    out = np.empty((n, P, T))
+    check(lib().bcm3hip_t4_draws_host(seed, n, P, T, out.ctypes.data), "bcm3hip_t4_draws_host")
+    return out
+
+
+WAIC_KEYS = ("count", "lppd", "mean", "p_waic", "elpd")
+
+
+def column_waic_host(data) -> dict:
+    """bcm3hip_column_waic_host: the WAIC kernel's source compiled for the host -- per column of data
+    [n, cols] of pointwise log-likelihoods (NaN = no value) count (int32), lppd, mean, p_waic, elpd
+    [cols]. Needs no device."""
+    x = np.ascontiguousarray(data, dtype=np.float64)
+    n, cols = x.shape
+    out = {k: np.empty(cols, dtype=np.int32 if k == "count" else np.float64) for k in WAIC_KEYS}
+    check(lib().bcm3hip_column_waic_host(n, cols, x.ctypes.data, *(out[k].ctypes.data for k in WAIC_KEYS)),
+          "bcm3hip_column_waic_host")
+    return out
+
+
+def column_waic(data) -> dict:
+    """bcm3hip_column_waic on data's device and torch's current stream: data is a CUDA float64 tensor
+    [n, cols]. Returns CUDA tensors under the keys of column_waic_host; the launch is asynchronous."""
+    import torch
+    x = data.contiguous()
+    n, cols = x.shape
+    out = {k: torch.empty(cols, dtype=torch.int32 if k == "count" else torch.float64, device=x.device)
+           for k in WAIC_KEYS}
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        check(lib().bcm3hip_column_waic(n, cols, x.data_ptr(), *(out[k].data_ptr() for k in WAIC_KEYS), stream),
+              "bcm3hip_column_waic")
+    return out
+
+
+# the outputs of bcm3hip_predict_obs in argument order: (key, leading shape, dtype); the [n, P, T]
+# arrays and scales come back only on request
+def predict_obs_outputs(n: int, k: int, P: int, T: int, pointwise: bool) -> dict:
+    f, i = np.float64, np.int32
+    out = dict(conc_q=np.empty((k, P, T)), conc_mean=np.empty((P, T)), conc_count=np.empty((P, T), dtype=i),
+               pred_q=np.empty((k, P, T)), pred_mean=np.empty((P, T)), pred_count=np.empty((P, T), dtype=i),
+               waic_count=np.empty((P, T), dtype=i), lppd=np.empty((P, T)), llh_mean=np.empty((P, T)),
+               p_waic=np.empty((P, T)), elpd=np.empty((P, T)), logp=np.empty(n), status=np.empty(n, dtype=i))
+    for key in ("conc", "ypred", "pll"):
+        out[key] = np.empty((n, P, T), dtype=f) if pointwise else None
+    out["scales"] = np.empty((n, 2), dtype=f) if pointwise else None
+    return out
+
+
+def predict_obs_pointers(out: dict):
+    return [None if v is None else v.ctypes.data for v in out.values()]
 
 
 STATS_DTYPE = np.dtype([(k, np.int32) for k in ("nst", "nfe", "nni", "nsetups", "nje", "netf", "ncfn", "nreinit")])
@@ -276,6 +339,16 @@ def lib() -> C.CDLL:
     L.bcm3hip_predict.restype = C.c_int
     L.bcm3hip_predict_last_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.bcm3hip_predict_last_ms.restype = C.c_int
+    L.bcm3hip_t4_draws_host.argtypes = [C.c_uint64, i64, i64, i64, vp]
+    L.bcm3hip_t4_draws_host.restype = C.c_int
+    L.bcm3hip_column_waic.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.bcm3hip_column_waic.restype = C.c_int
+    L.bcm3hip_column_waic_host.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp]
+    L.bcm3hip_column_waic_host.restype = C.c_int
+    L.bcm3hip_predict_obs.argtypes = [vp, sz, sz, vp, C.c_uint64, C.c_int, vp] + [vp] * 17
+    L.bcm3hip_predict_obs.restype = C.c_int
+    L.bcm3hip_predict_obs_last_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 4
+    L.bcm3hip_predict_obs_last_ms.restype = C.c_int
     for f in ("bcm3hip_open_popk", "bcm3hip_open_analytic", "bcm3hip_open_mixture", "bcm3hip_open_expm_pk", "bcm3hip_close", "bcm3hip_set_option",
               "bcm3hip_num_variables", "bcm3hip_eval_batch", "bcm3hip_eval_batch_device",
               "bcm3hip_last_kernel_ms", "bcm3hip_eval_batch_detail"):
@@ -318,6 +391,7 @@ class Context:
         self.h = handle
         self.d, self.P, self.N, self.T = d, P, N, T
         self.time = np.empty(0)  # PopPK contexts: the output times [T]
+        self.observed = np.empty((0, 0))  # PopPK contexts: the observations [P, T]
         self._keep = keep
 
     @classmethod
@@ -341,6 +415,7 @@ class Context:
         check(lib().bcm3hip_open_popk(device, C.byref(m), C.byref(h)), "bcm3hip_open_popk")
         ctx = cls(h, int(m.d), int(m.P), int(m.N), int(m.T))
         ctx.time = popk_time(m)
+        ctx.observed = popk_observed(m)
         return ctx
 
     @classmethod
@@ -351,6 +426,7 @@ class Context:
         check(lib().bcm3hip_open_popk(device, C.byref(m), C.byref(h)), "bcm3hip_open_popk")
         ctx = cls(h, int(m.d), int(m.P), int(m.N), int(m.T))
         ctx.time = popk_time(m)
+        ctx.observed = popk_observed(m)
         return ctx
 
     @classmethod
@@ -446,6 +522,26 @@ class Context:
         qms, tms = C.c_float(), C.c_float()
         check(lib().bcm3hip_predict_last_ms(self.h, C.byref(qms), C.byref(tms)), "bcm3hip_predict_last_ms")
         return float(qms.value), float(tms.value)
+
+    def predict_obs(self, values: np.ndarray, probs, seed: int = 0, pointwise: bool = False) -> dict:
+        """bcm3hip_predict_obs (PopPK contexts): predicted measurements of values [n, d] -- the bands of
+        the concentration and of the noisy prediction (conc_q, pred_q [n_probs, P, T] with _mean and
+        _count [P, T]), the WAIC terms per observation (waic_count, lppd, llh_mean, p_waic, elpd [P, T]),
+        logp, status [n]; with pointwise also conc, ypred, pll [n, P, T] and scales [n, 2]."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        out = predict_obs_outputs(n, p.size, self.P, self.T, pointwise)
+        check(lib().bcm3hip_predict_obs(self.h, n, self.d, _ptr(v), int(seed) & (2**64 - 1), p.size, _ptr(p),
+                                        *predict_obs_pointers(out)), "bcm3hip_predict_obs")
+        return {k: a for k, a in out.items() if a is not None}
+
+    def predict_obs_last_ms(self):
+        """(observation kernel, quantile launches, WAIC kernel, whole call) ms of the last predict_obs, by
+        HIP events on the context's stream"""
+        ms = [C.c_float() for _ in range(4)]
+        check(lib().bcm3hip_predict_obs_last_ms(self.h, *(C.byref(x) for x in ms)), "bcm3hip_predict_obs_last_ms")
+        return tuple(float(x.value) for x in ms)
 
     def eval_device(self, n: int, values_ptr: int, logp_ptr: int, status_ptr: Optional[int] = None,
                     stream: Optional[int] = None):

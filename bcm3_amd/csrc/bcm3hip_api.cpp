@@ -20,6 +20,7 @@
 #include "dev_buf.h"
 #include "incucyte_kernel.h"
 #include "popk_kernel.h"
+#include "predict_obs.h"
 #include "predict_quantile.h"
 
 const xm::GlibcPow* bcm3_pow_tables(int* from_libm);  // libm_tables.cpp
@@ -91,6 +92,13 @@ struct bcm3hip_ctx {
         DevBuf<int32_t> pred_count;
         hipEvent_t pred_ev[4] = {nullptr, nullptr, nullptr, nullptr};
         bool pred_timed = false;
+        // bcm3hip_predict_obs: conc, ypred, pll [n][P][T] and scales [n][2]; the bands of conc and
+        // ypred; the WAIC terms of pll ([4][P*T]: lppd, mean, p_waic, elpd); its event pairs (whole
+        // call, then the boundaries of the observation kernel, the quantile launches, the WAIC kernel)
+        DevBuf<double> obs_conc, obs_ypred, obs_pll, obs_scales, obs_cq, obs_cmean, obs_pq, obs_pmean, obs_waic;
+        DevBuf<int32_t> obs_ccount, obs_pcount, obs_wcount;
+        hipEvent_t obs_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        bool obs_timed = false;
     } popk;
     AnalyticDevModel am{};
     struct {
@@ -662,6 +670,8 @@ int bcm3hip_close(bcm3hip_ctx* c)
     for (hipEvent_t e : c->log_ev) hipEventDestroy(e);
     for (hipEvent_t e : c->popk.pred_ev)
         if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->popk.obs_ev)
+        if (e) hipEventDestroy(e);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return 0;
@@ -1050,6 +1060,96 @@ int bcm3hip_predict_last_ms(bcm3hip_ctx* c, float* quantile_ms, float* total_ms)
     auto& b = c->popk;
     if (quantile_ms) HIPCHK(hipEventElapsedTime(quantile_ms, b.pred_ev[2], b.pred_ev[3]));
     if (total_ms) HIPCHK(hipEventElapsedTime(total_ms, b.pred_ev[0], b.pred_ev[1]));
+    return 0;
+}
+
+int bcm3hip_predict_obs(bcm3hip_ctx* c, size_t n, size_t d, const double* values, uint64_t seed, int n_probs,
+                        const double* probs, double* conc_q, double* conc_mean, int32_t* conc_count, double* pred_q,
+                        double* pred_mean, int32_t* pred_count, int32_t* waic_count, double* lppd, double* llh_mean,
+                        double* p_waic, double* elpd, double* logp, int32_t* status, double* conc, double* ypred,
+                        double* pll, double* scales)
+{
+    if (!c || c->kind != Kind::PopK || (int)d != c->d || !values || !probs || !conc_q || !pred_q || !logp)
+        return BCM3HIP_ERR_ARG;
+    if (n < 1 || n > (size_t)PREDICT_MAX_N || n_probs < 1 || n_probs > PREDICT_MAX_PROBS) return BCM3HIP_ERR_ARG;
+    PredictProbs pr{};
+    for (int k = 0; k < n_probs; k++) {
+        if (!(probs[k] >= 0.0 && probs[k] <= 1.0)) return BCM3HIP_ERR_ARG;
+        pr.p[k] = probs[k];
+    }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(predict_obs_prepare_device());
+    auto& b = c->popk;
+    const size_t cols = (size_t)b.m.P * (size_t)b.m.T;  // conc, ypred, pll [n][P][T] as data[n][cols]
+    const size_t nq = (size_t)n_probs * cols;
+    if (b.traj.grow(n * cols * (size_t)b.m.N, kFloor) || b.obs_conc.grow(n * cols, kFloor) ||
+        b.obs_ypred.grow(n * cols, kFloor) || b.obs_pll.grow(n * cols, kFloor) || b.obs_scales.grow(2 * n, kFloor) ||
+        b.obs_cq.grow(nq, kFloor) || b.obs_pq.grow(nq, kFloor) || b.obs_cmean.grow(cols, kFloor) ||
+        b.obs_pmean.grow(cols, kFloor) || b.obs_waic.grow(4 * cols, kFloor) || b.obs_ccount.grow(cols, kFloor) ||
+        b.obs_pcount.grow(cols, kFloor) || b.obs_wcount.grow(cols, kFloor))
+        return BCM3HIP_ERR_ALLOC;
+    for (hipEvent_t& e : b.obs_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    b.obs_timed = false;
+    HIPCHK(hipEventRecord(b.obs_ev[0], c->stream));
+    int r = stage_batch(c, n, d, values);
+    if (r == 0) r = launch(c, n, c->values, c->logp, c->status, b.traj, nullptr, c->stream);
+    if (r) return r;
+    double* const w = b.obs_waic;
+    HIPCHK(hipEventRecord(b.obs_ev[2], c->stream));
+    hipError_t e = launch_predict_obs(b.m, (int64_t)n, c->values, b.traj, seed, b.obs_conc, b.obs_ypred, b.obs_pll,
+                                      b.obs_scales, c->stream);
+    HIPCHK(hipEventRecord(b.obs_ev[3], c->stream));
+    if (e == hipSuccess)
+        e = launch_predict_quantiles((int64_t)n, (int64_t)cols, b.obs_conc, n_probs, pr, b.obs_cq, b.obs_cmean, b.obs_ccount,
+                                     c->stream);
+    if (e == hipSuccess)
+        e = launch_predict_quantiles((int64_t)n, (int64_t)cols, b.obs_ypred, n_probs, pr, b.obs_pq, b.obs_pmean,
+                                     b.obs_pcount, c->stream);
+    HIPCHK(hipEventRecord(b.obs_ev[4], c->stream));
+    if (e == hipSuccess)
+        e = launch_predict_waic((int64_t)n, (int64_t)cols, b.obs_pll, b.obs_wcount, w, w + cols, w + 2 * cols, w + 3 * cols,
+                                c->stream);
+    HIPCHK(hipEventRecord(b.obs_ev[5], c->stream));
+    if (e != hipSuccess) {
+        fprintf(stderr, "bcm3hip: predictive-check kernel launch failed: %s\n", hipGetErrorString(e));
+        return BCM3HIP_ERR_HIP;
+    }
+    auto back = [&](void* dst, const void* src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    const size_t cb = cols * sizeof(double), ci = cols * sizeof(int32_t), full = n * cols * sizeof(double);
+    HIPCHK(back(logp, c->logp, n * sizeof(double)));
+    HIPCHK(back(status, c->status, n * sizeof(int32_t)));
+    HIPCHK(back(conc_q, b.obs_cq, nq * sizeof(double)));
+    HIPCHK(back(conc_mean, b.obs_cmean, cb));
+    HIPCHK(back(conc_count, b.obs_ccount, ci));
+    HIPCHK(back(pred_q, b.obs_pq, nq * sizeof(double)));
+    HIPCHK(back(pred_mean, b.obs_pmean, cb));
+    HIPCHK(back(pred_count, b.obs_pcount, ci));
+    HIPCHK(back(waic_count, b.obs_wcount, ci));
+    HIPCHK(back(lppd, w, cb));
+    HIPCHK(back(llh_mean, w + cols, cb));
+    HIPCHK(back(p_waic, w + 2 * cols, cb));
+    HIPCHK(back(elpd, w + 3 * cols, cb));
+    HIPCHK(back(conc, b.obs_conc, full));
+    HIPCHK(back(ypred, b.obs_ypred, full));
+    HIPCHK(back(pll, b.obs_pll, full));
+    HIPCHK(back(scales, b.obs_scales, 2 * n * sizeof(double)));
+    HIPCHK(hipEventRecord(b.obs_ev[1], c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    b.obs_timed = true;
+    return 0;
+}
+
+int bcm3hip_predict_obs_last_ms(bcm3hip_ctx* c, float* obs_ms, float* quantile_ms, float* waic_ms, float* total_ms)
+{
+    if (!c || c->kind != Kind::PopK || !c->popk.obs_timed) return BCM3HIP_ERR_ARG;
+    auto& b = c->popk;
+    if (obs_ms) HIPCHK(hipEventElapsedTime(obs_ms, b.obs_ev[2], b.obs_ev[3]));
+    if (quantile_ms) HIPCHK(hipEventElapsedTime(quantile_ms, b.obs_ev[3], b.obs_ev[4]));
+    if (waic_ms) HIPCHK(hipEventElapsedTime(waic_ms, b.obs_ev[4], b.obs_ev[5]));
+    if (total_ms) HIPCHK(hipEventElapsedTime(total_ms, b.obs_ev[0], b.obs_ev[1]));
     return 0;
 }
 

@@ -13,6 +13,12 @@
 //   component selection (RNG::Sample) uniform key 0xA001
 //   TestSample                       uniform key 0xC000
 // (tests/ptmh_reference.py and tests/proposal_reference.py restate the same map.)
+//
+// Key map of the posterior-predictive noise draws (predict_obs.h; no sampler iteration or chain is
+// involved, so the two middle words carry the draw's row and the patient):
+//   Student-t(4) variate of (row e, patient j, time index t): rng_key(seed, e, j, k) with
+//   k = 0x10000 + 64 t + 2 a (u) and k + 1 (v) for attempt a = 0..31 of Bailey's polar method
+// Every k is >= 0x10000, above all slots of the map above. (tests/predict_obs_reference.py restates it.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,7 +27,7 @@
 namespace bcm3hip {
 namespace rng {
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x)
+__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x)
 {
     x += 0x9E3779B97F4A7C15ull;
     uint64_t z = x;
@@ -31,10 +37,10 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x)
 }
 
 // uniform in [0, 1) from 53 random bits
-__device__ __forceinline__ double u01(uint64_t z) { return (double)(z >> 11) * (1.0 / 9007199254740992.0); }
+__host__ __device__ __forceinline__ double u01(uint64_t z) { return (double)(z >> 11) * (1.0 / 9007199254740992.0); }
 
-// key for (seed, iteration, chain, slot); slot < 2^16
-__device__ __forceinline__ uint64_t rng_key(uint64_t seed, uint64_t iter, uint64_t chain, uint64_t slot)
+// key for (seed, iteration, chain, slot); slot < 2^16 in the sampler's map
+__host__ __device__ __forceinline__ uint64_t rng_key(uint64_t seed, uint64_t iter, uint64_t chain, uint64_t slot)
 {
     return splitmix64(splitmix64(seed) ^ (iter * 0x100000001B3ull) ^ (chain * 0xC2B2AE3D27D4EB4Full) ^
                       (slot * 0x165667B19E3779F9ull));
@@ -62,6 +68,7 @@ enum : uint64_t {
     KEY_UPDATE = 0xA000,
     KEY_SELECT = 0xA001,
     KEY_ACCEPT = 0xC000,
+    KEY_PREDICT_T4 = 0x10000,
 };
 
 }  // namespace rng

@@ -180,6 +180,35 @@ int bcm3_likelihood_predict(bcm3_likelihood* h, size_t n, const double* values, 
     return bcm3_likelihood_predict_status(h, n, values, n_probs, probs, q, mean, count, logp, nullptr);
 }
 
+int bcm3_likelihood_predict_obs(bcm3_likelihood* h, size_t n, const double* values, uint64_t seed, int n_probs,
+                                const double* probs, double* conc_q, double* conc_mean, int32_t* conc_count,
+                                double* pred_q, double* pred_mean, int32_t* pred_count, int32_t* waic_count, double* lppd,
+                                double* llh_mean, double* p_waic, double* elpd, double* logp, int32_t* status,
+                                double* conc, double* ypred, double* pll, double* scales)
+{
+    if (!h || !h->ll) return -1;
+    bcm3::LikelihoodGPUBase* p = dynamic_cast<bcm3::LikelihoodPopPKTrajectory*>(h->ll.get());
+    if (!p) p = dynamic_cast<bcm3::LikelihoodPharmacokineticTrajectory*>(h->ll.get());
+    if (!p) {
+        LOGERROR("predicted measurements need a likelihood with a trajectory output (pop_pk_trajectory or "
+                 "pharmacokinetic_trajectory)");
+        return -2;
+    }
+    if (!p->Context()) {
+        LOGERROR("predicted measurements need a device; the likelihood was created without one");
+        return -2;
+    }
+    const int r = bcm3hip_predict_obs(p->Context(), n, p->GetNumVariables(), values, seed, n_probs, probs, conc_q,
+                                      conc_mean, conc_count, pred_q, pred_mean, pred_count, waic_count, lppd, llh_mean,
+                                      p_waic, elpd, logp, status, conc, ypred, pll, scales);
+    if (r) {
+        LOGERROR("bcm3hip_predict_obs: %s (at most %d parameter vectors and %d probabilities in [0, 1] per call)",
+                 bcm3hip_error_string(r), BCM3HIP_PREDICT_MAX_N, BCM3HIP_PREDICT_MAX_PROBS);
+        return -3;
+    }
+    return 0;
+}
+
 int64_t bcm3_likelihood_ccm_track(const bcm3_likelihood* h, double* data, int64_t cap, int32_t* track_ix)
 {
     if (!h || !h->ll) return -1;

@@ -35,6 +35,7 @@ def lib() -> C.CDLL:
     L.bcm3_likelihood_incucyte_detail.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
     L.bcm3_likelihood_predict.argtypes = [vp, sz, vp, C.c_int, vp, vp, vp, vp, vp]
     L.bcm3_likelihood_predict_status.argtypes = [vp, sz, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.bcm3_likelihood_predict_obs.argtypes = [vp, sz, vp, C.c_uint64, C.c_int, vp] + [vp] * 17
     L.bcm3_likelihood_ccm_track.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int32)]
     L.bcm3_likelihood_ccm_track.restype = C.c_int64
     L.bcm3_table_read.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_int64), vp, C.c_int64]
@@ -184,6 +185,28 @@ class Likelihood:
         if r != 0:
             _err("bcm3_likelihood_predict", r)
         out["time"] = _hip.popk_time(m)
+        return out
+
+    def predict_obs(self, values, probs, seed: int = 0, pointwise: bool = False) -> dict:
+        """pop_pk_trajectory / pharmacokinetic_trajectory: predicted measurements of values [n, d]
+        (bcm3_likelihood_predict_obs; bcm3_amd.predict.measurements is the front end), the arrays of
+        _hip.Context.predict_obs plus time [T] and observed [P, T]."""
+        try:
+            m = self.popk_model()
+        except RuntimeError:
+            m = None  # the library call below refuses the type with its own message
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        P, T = (int(m.P), int(m.T)) if m is not None else (0, 0)
+        out = _hip.predict_obs_outputs(n, p.size, P, T, pointwise)
+        r = lib().bcm3_likelihood_predict_obs(self.h, n, v.ctypes.data, int(seed) & (2**64 - 1), p.size, p.ctypes.data,
+                                              *_hip.predict_obs_pointers(out))
+        if r != 0:
+            _err("bcm3_likelihood_predict_obs", r)
+        out = {k: a for k, a in out.items() if a is not None}
+        out["time"] = _hip.popk_time(m)
+        out["observed"] = _hip.popk_observed(m)
         return out
 
     def ccm_track(self):

@@ -15,6 +15,28 @@ MAX_SAMPLES = _hip.PREDICT_MAX_N
 MAX_PROBS = _hip.PREDICT_MAX_PROBS
 
 
+def _check(ll, samples, probs, what):
+    """samples as [n, d] and probs as an array, within the limits of one device call"""
+    v = np.ascontiguousarray(samples, dtype=np.float64)
+    if v.ndim == 1:
+        v = v.reshape(1, -1)
+    if v.ndim != 2 or v.shape[1] != ll.d:
+        raise ValueError(f"samples must be [n, {ll.d}] (one row per draw, the likelihood's {ll.d} variables), "
+                         f"got {v.shape}")
+    n = v.shape[0]
+    if n < 1:
+        raise ValueError(f"{what} needs at least one sample")
+    if n > MAX_SAMPLES:
+        raise ValueError(f"{n} samples: {what} takes at most {MAX_SAMPLES} per call (one workgroup "
+                         f"sorts a column in LDS); thin the draws, e.g. samples[::{-(-n // MAX_SAMPLES)}]")
+    p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    if not 1 <= p.size <= MAX_PROBS:
+        raise ValueError(f"between 1 and {MAX_PROBS} probabilities per call, got {p.size}")
+    if not np.all((p >= 0.0) & (p <= 1.0)):  # NaN fails both
+        raise ValueError(f"probabilities must lie in [0, 1], got {p.tolist()}")
+    return v, p
+
+
 def posterior_predictive(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95)) -> dict:
     """The bands of samples [n, d] (parameter vectors in the likelihood's variable order) under a
     bcm3_amd.likelihood.Likelihood or a PopPK bcm3_amd._hip.Context:
@@ -28,23 +50,7 @@ def posterior_predictive(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95)
 
     At most MAX_SAMPLES (8192) samples per call: more raises ValueError -- thin the draws first."""
     ll = likelihood_or_context
-    v = np.ascontiguousarray(samples, dtype=np.float64)
-    if v.ndim == 1:
-        v = v.reshape(1, -1)
-    if v.ndim != 2 or v.shape[1] != ll.d:
-        raise ValueError(f"samples must be [n, {ll.d}] (one row per draw, the likelihood's {ll.d} variables), "
-                         f"got {v.shape}")
-    n = v.shape[0]
-    if n < 1:
-        raise ValueError("posterior_predictive needs at least one sample")
-    if n > MAX_SAMPLES:
-        raise ValueError(f"{n} samples: posterior_predictive takes at most {MAX_SAMPLES} per call (one workgroup "
-                         f"sorts a column in LDS); thin the draws, e.g. samples[::{-(-n // MAX_SAMPLES)}]")
-    p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
-    if not 1 <= p.size <= MAX_PROBS:
-        raise ValueError(f"between 1 and {MAX_PROBS} probabilities per call, got {p.size}")
-    if not np.all((p >= 0.0) & (p <= 1.0)):  # NaN fails both
-        raise ValueError(f"probabilities must lie in [0, 1], got {p.tolist()}")
+    v, p = _check(ll, samples, probs, "posterior_predictive")
     out = ll.predict(v, p)
     if "time" not in out:
         out["time"] = np.array(ll.time, dtype=np.float64)
@@ -93,3 +99,71 @@ def from_output(path: str, likelihood, temperature_index: int = -1, burn_in: int
     the variable."""
     rows = select_samples(path, getattr(likelihood, "variable_names", None), temperature_index, burn_in, thin)
     return posterior_predictive(likelihood, rows, probs)
+
+
+def coverage(observed, lower, upper) -> np.ndarray:
+    """per patient the share of observed points (not NaN, and with a band there) inside [lower, upper];
+    NaN for a patient without such points. All arrays [P, T]."""
+    obs = np.asarray(observed, dtype=np.float64)
+    have = ~np.isnan(obs) & ~np.isnan(lower) & ~np.isnan(upper)
+    with np.errstate(invalid="ignore"):
+        inside = have & (obs >= lower) & (obs <= upper)
+    cnt = have.sum(axis=1)
+    return np.where(cnt > 0, inside.sum(axis=1) / np.maximum(cnt, 1), np.nan)
+
+
+def waic_totals(count, lppd, p_waic, elpd) -> dict:
+    """the totals over the observations with at least two draws (count >= 2: the points whose p_waic
+    exists): elpd_waic, p_waic, lppd, n_obs and se = sqrt(n_obs var(elpd_i)), var with denominator
+    n_obs - 1 (NaN for fewer than two points)"""
+    use = np.asarray(count) >= 2
+    n_obs = int(use.sum())
+    e = np.asarray(elpd)[use]
+    se = float(np.sqrt(n_obs * np.var(e, ddof=1))) if n_obs >= 2 else float("nan")
+    return dict(elpd_waic=float(e.sum()), p_waic=float(np.asarray(p_waic)[use].sum()),
+                lppd=float(np.asarray(lppd)[use].sum()), se=se, n_obs=n_obs)
+
+
+def measurements(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95), seed: int = 0, pointwise: bool = False) -> dict:
+    """Predicted measurements of samples [n, d] under a pop_pk_trajectory / pharmacokinetic_trajectory
+    Likelihood or a PopPK Context: what can be laid over the data.
+
+      concentration  dict(quantiles [len(probs), P, T], mean, count [P, T]) of conversion * y1, the
+                     quantity the likelihood observes, over the draws that reached the time point
+      predicted      the same of concentration + (sd + sd2 max(concentration, 0)) tau, tau a Student-t(4)
+                     draw of the likelihood's error model on the counter-based stream `seed`
+      observed, time [P, T], [T]
+      coverage       [P] the share of a patient's observed points between the lowest and the highest
+                     predicted quantile
+      waic           per observation [P, T]: count, lppd, mean, p_waic, elpd (NaN where nothing was
+                     observed); and the totals elpd_waic, p_waic_total, lppd_total, se, n_obs over the
+                     points with count >= 2
+      logp, status   [n] as evaluate_batch returns them
+      pointwise=True also concentration_draws, predicted_draws, pointwise_llh [n, P, T], scales [n, 2]
+
+    At most MAX_SAMPLES (8192) samples per call: more raises ValueError -- thin the draws first."""
+    ll = likelihood_or_context
+    v, p = _check(ll, samples, probs, "measurements")
+    raw = ll.predict_obs(v, p, seed=seed, pointwise=pointwise)
+    observed = raw["observed"] if "observed" in raw else np.array(ll.observed, dtype=np.float64)
+    out = dict(concentration=dict(quantiles=raw["conc_q"], mean=raw["conc_mean"], count=raw["conc_count"]),
+               predicted=dict(quantiles=raw["pred_q"], mean=raw["pred_mean"], count=raw["pred_count"]),
+               observed=observed, time=raw["time"] if "time" in raw else np.array(ll.time, dtype=np.float64),
+               logp=raw["logp"], status=raw["status"])
+    order = np.argsort(p, kind="stable")
+    out["coverage"] = coverage(observed, raw["pred_q"][order[0]], raw["pred_q"][order[-1]])
+    tot = waic_totals(raw["waic_count"], raw["lppd"], raw["p_waic"], raw["elpd"])
+    out["waic"] = dict(count=raw["waic_count"], lppd=raw["lppd"], mean=raw["llh_mean"], p_waic=raw["p_waic"],
+                       elpd=raw["elpd"], elpd_waic=tot["elpd_waic"], p_waic_total=tot["p_waic"],
+                       lppd_total=tot["lppd"], se=tot["se"], n_obs=tot["n_obs"])
+    if pointwise:
+        out.update(concentration_draws=raw["conc"], predicted_draws=raw["ypred"], pointwise_llh=raw["pll"],
+                   scales=raw["scales"])
+    return out
+
+
+def measurements_from_output(path: str, likelihood, temperature_index: int = -1, burn_in: int = 0, thin: int = 1,
+                             probs=(0.05, 0.5, 0.95), seed: int = 0, pointwise: bool = False) -> dict:
+    """measurements on the samples of an output.nc, selected and checked as from_output does"""
+    rows = select_samples(path, getattr(likelihood, "variable_names", None), temperature_index, burn_in, thin)
+    return measurements(likelihood, rows, probs, seed, pointwise)

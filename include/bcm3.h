@@ -62,6 +62,17 @@ int bcm3_likelihood_predict(bcm3_likelihood* ll, size_t n, const double* values,
 int bcm3_likelihood_predict_status(bcm3_likelihood* ll, size_t n, const double* values, int n_probs,
                                    const double* probs, double* q, double* mean, int32_t* count, double* logp,
                                    int32_t* status);
+/* Predicted measurements (bcm3hip_predict_obs on the likelihood's context; see bcm3hip.h for every
+ * array): the bands conc_q / pred_q[n_probs][P][T] of the concentration the likelihood observes and
+ * of that concentration plus a Student-t(4) noise draw of the error model (seeded by `seed`), their
+ * mean and count [P][T], the WAIC terms per observation [P][T], logp[n] and status[n]; conc, ypred,
+ * pll [n][P][T] and scales [n][2] where the pointer is not NULL. Every output but conc_q, pred_q and
+ * logp may be NULL. Return values as bcm3_likelihood_predict. */
+int bcm3_likelihood_predict_obs(bcm3_likelihood* ll, size_t n, const double* values, uint64_t seed, int n_probs,
+                                const double* probs, double* conc_q, double* conc_mean, int32_t* conc_count,
+                                double* pred_q, double* pred_mean, int32_t* pred_count, int32_t* waic_count, double* lppd,
+                                double* llh_mean, double* p_waic, double* elpd, double* logp, int32_t* status,
+                                double* conc, double* ypred, double* pll, double* scales);
 /* cell_cycle_marker: the track the likelihood evaluates against (the row ccm.track_ix selected):
  * copies up to cap frames into data (may be NULL) and the row index into *track_ix (may be NULL);
  * returns the number of frames, -2 for other likelihood types. */

@@ -905,6 +905,51 @@ int bcm3hip_predict(bcm3hip_ctx* ctx, size_t n, size_t d, const double* values, 
  * kernel alone, and the whole call from the upload of values to the last copy back. */
 int bcm3hip_predict_last_ms(bcm3hip_ctx* ctx, float* quantile_ms, float* total_ms);
 
+/* ---- Measurement-level predictive checks (predict_obs_kernels.hip) ----
+ * tau[n][P][T]: the Student-t(4) variate bcm3hip_predict_obs adds, scaled, to the concentration of
+ * (row e, patient j, time index t). It depends on (seed, e, j, t) alone -- not on n, P, T or the
+ * launch -- by Bailey's polar method on counter-based uniforms (the key map is in ctr_rng.h): u, v
+ * on [-1, 1), w = u*u + v*v, the pair rejected when w > 1 or w == 0, else
+ * tau = u * sqrt(4 * (1 / sqrt(w) - 1) / w); NaN after 32 rejections. Needs no device.
+ * 1 <= n <= BCM3HIP_PREDICT_MAX_N, else BCM3HIP_ERR_ARG. */
+int bcm3hip_t4_draws_host(uint64_t seed, int64_t n, int64_t P, int64_t T, double* out);
+/* WAIC terms per column of a row-major data[n][cols] of pointwise log-likelihoods l, NaN meaning "no
+ * value": count[col] = m, lppd = (M + log(sum exp(l - M))) - log(m) with M the column's maximum,
+ * mean = (sum l) / m, p_waic = sum (l - mean)^2 / (m - 1) (NaN for m < 2), elpd = lppd - p_waic;
+ * m = 0 gives NaN throughout. Summation order: partial k of 64 takes the rows r = k, k + 64, ... in
+ * rising r, and the 64 partials are added in the order 0..63. exp and log are correctly rounded.
+ * Limits: 1 <= n <= BCM3HIP_PREDICT_MAX_N, cols >= 0, no NULL pointer when cols > 0; anything else
+ * is BCM3HIP_ERR_ARG before any launch.
+ * On device buffers, on the current device, asynchronous on `stream`. */
+int bcm3hip_column_waic(int64_t n, int64_t cols, const double* data_dev, int32_t* count_dev, double* lppd_dev,
+                        double* mean_dev, double* pwaic_dev, double* elpd_dev, void* stream);
+/* The same source compiled for the host, host buffers throughout; needs no device. Bit-identical to
+ * the kernel. */
+int bcm3hip_column_waic_host(int64_t n, int64_t cols, const double* data, int32_t* count, double* lppd, double* mean,
+                             double* pwaic, double* elpd);
+/* Predicted measurements of n parameter vectors (PopPK contexts only; other kinds: BCM3HIP_ERR_ARG).
+ * Stages and solves values[n][d] as bcm3hip_predict does, then on the device, per (draw e, patient j,
+ * time index t):
+ *   conc  = conversion * y1, conversion = (1e6 / MW) / vod: what the likelihood observes; NaN where
+ *           the trajectory is NaN and for t >= simulate_until[j]
+ *   pll   = LogPdfTnu4(conc, observed[j][t], sd + sd2 * max(conc, 0)), the term the solve kernel added
+ *           to the patient's log-likelihood, bit for bit; NaN where observed or conc is NaN
+ *   ypred = conc + (sd + sd2 * max(conc, 0)) * tau(seed, e, j, t)
+ * and scales[e] = (sd, sd2). It then reduces conc and ypred to bands (bcm3hip_column_quantiles over
+ * P*T columns each) and pll to WAIC terms (bcm3hip_column_waic), all on the context's stream, and
+ * copies back conc_q / pred_q [n_probs][P][T], their mean and count [P][T] (may be NULL), the five
+ * WAIC arrays [P][T] (may be NULL), logp[n] and status[n] (may be NULL). conc, ypred, pll [n][P][T]
+ * and scales [n][2] are copied back only where the pointer is not NULL. Synchronous. */
+int bcm3hip_predict_obs(bcm3hip_ctx* ctx, size_t n, size_t d, const double* values, uint64_t seed, int n_probs,
+                        const double* probs, double* conc_q, double* conc_mean, int32_t* conc_count, double* pred_q,
+                        double* pred_mean, int32_t* pred_count, int32_t* waic_count, double* lppd, double* llh_mean,
+                        double* p_waic, double* elpd, double* logp, int32_t* status, double* conc, double* ypred,
+                        double* pll, double* scales);
+/* HIP-event times of the last bcm3hip_predict_obs of the context (any may be NULL): the observation
+ * kernel, the two quantile launches, the WAIC kernel, and the whole call from the upload of values
+ * to the last copy back. */
+int bcm3hip_predict_obs_last_ms(bcm3hip_ctx* ctx, float* obs_ms, float* quantile_ms, float* waic_ms, float* total_ms);
+
 /* ---- Importance sampler (is_kernels.hip) ----
  * SamplerIS::RunImpl (src/sampler/SamplerIS.cpp:49-87) in batches: draw from the prior, evaluate the
  * likelihood (bcm3hip_eval_batch_device), keep every draw whose log-weight is within 23.02585 of the
