@@ -237,6 +237,55 @@ def column_waic(data) -> dict:
     return out
 
 
+CHAIN_KEYS = ("mean", "sd", "rho1", "ess", "decorrelation_lag", "first_negative_lag", "flags")
+CHAIN_INT_KEYS = ("decorrelation_lag", "first_negative_lag", "flags")
+CHAIN_NONFINITE, CHAIN_CONSTANT, CHAIN_NO_NEGATIVE_LAG = 1, 2, 4  # BCM3HIP_CHAIN_*
+
+
+def chain_max_lag(n: int) -> int:
+    """L = min(n // 2, n - 1), the last lag of the autocorrelation function (R's lag.max = length / 2)"""
+    return min(n // 2, n - 1)
+
+
+def column_chain_stats_host(data, max_lag_out=None) -> dict:
+    """bcm3hip_column_chain_stats_host: the chain kernel's source compiled for the host -- per column of
+    data [n, cols] mean, sd, rho1, ess (float64), decorrelation_lag, first_negative_lag, flags (int32)
+    [cols]; with max_lag_out also acf [max_lag_out + 1, cols]. Needs no device."""
+    x = np.ascontiguousarray(data, dtype=np.float64)
+    n, cols = x.shape
+    out = {k: np.empty(cols, dtype=np.int32 if k in CHAIN_INT_KEYS else np.float64) for k in CHAIN_KEYS}
+    acf = None if max_lag_out is None else np.empty((max(int(max_lag_out), 0) + 1, cols))
+    check(lib().bcm3hip_column_chain_stats_host(n, cols, x.ctypes.data, *(out[k].ctypes.data for k in CHAIN_KEYS),
+                                                0 if max_lag_out is None else int(max_lag_out),
+                                                None if acf is None else acf.ctypes.data),
+          "bcm3hip_column_chain_stats_host")
+    if acf is not None:
+        out["acf"] = acf
+    return out
+
+
+def column_chain_stats(data, max_lag_out=None) -> dict:
+    """bcm3hip_column_chain_stats on data's device and torch's current stream: data is a CUDA float64
+    tensor [n, cols]. Returns CUDA tensors under the keys of column_chain_stats_host; the launch is
+    asynchronous."""
+    import torch
+    x = data.contiguous()
+    n, cols = x.shape
+    out = {k: torch.empty(cols, dtype=torch.int32 if k in CHAIN_INT_KEYS else torch.float64, device=x.device)
+           for k in CHAIN_KEYS}
+    acf = None if max_lag_out is None else torch.empty((max(int(max_lag_out), 0) + 1, cols), dtype=torch.float64,
+                                                       device=x.device)
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        check(lib().bcm3hip_column_chain_stats(n, cols, x.data_ptr(), *(out[k].data_ptr() for k in CHAIN_KEYS),
+                                               0 if max_lag_out is None else int(max_lag_out),
+                                               None if acf is None else acf.data_ptr(), stream),
+              "bcm3hip_column_chain_stats")
+    if acf is not None:
+        out["acf"] = acf
+    return out
+
+
 # the outputs of bcm3hip_predict_obs in argument order: (key, leading shape, dtype); the [n, P, T]
 # arrays and scales come back only on request
 def predict_obs_outputs(n: int, k: int, P: int, T: int, pointwise: bool) -> dict:
@@ -345,6 +394,10 @@ def lib() -> C.CDLL:
     L.bcm3hip_column_waic.restype = C.c_int
     L.bcm3hip_column_waic_host.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp]
     L.bcm3hip_column_waic_host.restype = C.c_int
+    L.bcm3hip_column_chain_stats.argtypes = [i64, i64] + [vp] * 8 + [C.c_int, vp, vp]
+    L.bcm3hip_column_chain_stats.restype = C.c_int
+    L.bcm3hip_column_chain_stats_host.argtypes = [i64, i64] + [vp] * 8 + [C.c_int, vp]
+    L.bcm3hip_column_chain_stats_host.restype = C.c_int
     L.bcm3hip_predict_obs.argtypes = [vp, sz, sz, vp, C.c_uint64, C.c_int, vp] + [vp] * 17
     L.bcm3hip_predict_obs.restype = C.c_int
     L.bcm3hip_predict_obs_last_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 4

@@ -211,8 +211,10 @@ void dump_to(const Json& j, std::string& o)
     case Json::Null: o += "null"; break;
     case Json::Bool: o += j.b ? "true" : "false"; break;
     case Json::Number:
-        if (!std::isfinite(j.num)) {
+        if (std::isnan(j.num)) {
             o += "null";
+        } else if (std::isinf(j.num)) {  // a log-likelihood of -inf is a value, not a fill: the literals json_parse reads
+            o += (j.num < 0) ? "-Infinity" : "Infinity";
         } else {
             char buf[32];
             snprintf(buf, sizeof buf, "%.17g", j.num);

@@ -91,6 +91,42 @@ def select_samples(path: str, variable_names=None, temperature_index: int = -1, 
     return np.ascontiguousarray(rows)
 
 
+def select_run(path: str, burn_in=None, thin: int = 1) -> dict:
+    """All temperatures of an output.nc (read by bcm3_amd.ptmh.read_data_file), without the first
+    burn_in samples, every thin-th of the rest: names [d], temperature [nt], values [n, nt, d],
+    log_likelihood and log_prior [n, nt], n_total, the number of samples in the file, and
+    max_log_likelihood over every written sample of the file (burn-in included, as R/load.r takes it).
+    burn_in=None drops the first half (n_total // 2 samples), the default sample_ix of R/stats.r. A
+    selected sample with a fill value in any of the three arrays was never written and is refused as
+    select_samples refuses it; a log-likelihood of -inf is a value."""
+    from .ptmh import read_data_file
+    doc = read_data_file(path)
+    s = doc.get("samples", {})
+    for key in ("variable_values", "variable", "temperature", "log_likelihood", "log_prior"):
+        if key not in s:
+            raise ValueError(f"{path}: no samples/{key}")
+    vals = np.array(s["variable_values"]["data"], dtype=np.float64)  # fill values (null) become NaN
+    if vals.ndim != 3:
+        raise ValueError(f"{path}: samples/variable_values has {vals.ndim} dimensions, expected 3")
+    n_total, nt, d = vals.shape
+    if burn_in is None:
+        burn_in = n_total // 2
+    if burn_in < 0 or thin < 1:
+        raise ValueError(f"burn_in must be >= 0 and thin >= 1, got {burn_in} and {thin}")
+    llh = np.array(s["log_likelihood"]["data"], dtype=np.float64).reshape(n_total, nt)
+    lpr = np.array(s["log_prior"]["data"], dtype=np.float64).reshape(n_total, nt)
+    written = llh[~np.isnan(llh)]
+    llh_max = float(written.max()) if written.size else float("nan")
+    vals, llh, lpr = vals[burn_in::thin], llh[burn_in::thin], lpr[burn_in::thin]
+    missing = np.flatnonzero(np.isnan(vals).any(axis=(1, 2)) | np.isnan(llh).any(axis=1) | np.isnan(lpr).any(axis=1))
+    if missing.size:
+        raise ValueError(f"{path}: sample {burn_in + thin * int(missing[0])} was never written "
+                         f"({missing.size} of the {vals.shape[0]} selected samples hold fill values)")
+    return dict(names=list(s["variable"]["data"]), temperature=np.array(s["temperature"]["data"], dtype=np.float64),
+                values=np.ascontiguousarray(vals), log_likelihood=np.ascontiguousarray(llh),
+                log_prior=np.ascontiguousarray(lpr), n_total=n_total, max_log_likelihood=llh_max)
+
+
 def from_output(path: str, likelihood, temperature_index: int = -1, burn_in: int = 0, thin: int = 1,
                 probs=(0.05, 0.5, 0.95)) -> dict:
     """posterior_predictive on the samples of an output.nc: temperature temperature_index (-1: the

@@ -950,6 +950,39 @@ int bcm3hip_predict_obs(bcm3hip_ctx* ctx, size_t n, size_t d, const double* valu
  * to the last copy back. */
 int bcm3hip_predict_obs_last_ms(bcm3hip_ctx* ctx, float* obs_ms, float* quantile_ms, float* waic_ms, float* total_ms);
 
+/* ---- Chain diagnostics (chain_stats_kernels.hip) ----
+ * Per column x[0..n-1] of a row-major data[n][cols], the quantities of R/stats.r's variable_summary:
+ *   mean = (sum x) / n,  c_k = sum_{t=0}^{n-1-k} (x_t - mean)(x_{t+k} - mean) for k = 0..L,
+ *   L = min(n / 2, n - 1) (R's acf(lag.max = length / 2)),  rho_k = c_k / c_0,
+ *   sd = sqrt(c_0 / (n - 1)),  rho1 = rho_1,
+ *   first_negative_lag F = the first k with rho_k < 0, or -1,
+ *   decorrelation_lag = the first k >= 0 with rho_k < 2 / sqrt(n), or -1: a lag, where R returns the
+ *     index k + 1,
+ *   ess = n / (1 + 2 (rho_1 + ... + rho_{F-1})), and n for F = 1. Without a negative lag up to L, where
+ *     R stops with an error, the sum runs through L and BCM3HIP_CHAIN_NO_NEGATIVE_LAG is set.
+ * flags[col] is 0 or one of the BCM3HIP_CHAIN_ values. A column with a NaN or infinite value (or whose
+ * c_0 overflows), and a constant one (all values equal, or c_0 == 0; n = 1 included), keep the mean
+ * as the sums give it (-inf stays -inf) and get NaN for sd, rho1, ess and acf, -1 for both lags.
+ * Summation order: a sum over t is 64 partials, partial r taking t = r, r + 64, ... in rising t; the
+ * partials are added as a binary tree (for s = 32, 16, ..., 1: partial i < s += partial i + s); the
+ * sum of rho_k runs in rising k. No fused multiply-add.
+ * acf (may be NULL) receives rho_k, k = 0..max_lag_out, at acf[k * cols + col].
+ * Limits: 1 <= n <= BCM3HIP_PREDICT_MAX_N, cols >= 0, 0 <= max_lag_out <= L, no NULL pointer but acf
+ * when cols > 0; anything else is BCM3HIP_ERR_ARG before any launch. cols == 0 launches nothing.
+ * On device buffers, on the current device, asynchronous on `stream`. */
+#define BCM3HIP_CHAIN_NONFINITE 1
+#define BCM3HIP_CHAIN_CONSTANT 2
+#define BCM3HIP_CHAIN_NO_NEGATIVE_LAG 4
+int bcm3hip_column_chain_stats(int64_t n, int64_t cols, const double* data_dev, double* mean_dev, double* sd_dev,
+                               double* rho1_dev, double* ess_dev, int32_t* decorrelation_lag_dev,
+                               int32_t* first_negative_lag_dev, int32_t* flags_dev, int max_lag_out,
+                               double* acf_dev /*[max_lag_out + 1][cols] or NULL*/, void* stream);
+/* The same source compiled for the host, host buffers throughout; needs no device. Bit-identical to
+ * the kernel. */
+int bcm3hip_column_chain_stats_host(int64_t n, int64_t cols, const double* data, double* mean, double* sd, double* rho1,
+                                    double* ess, int32_t* decorrelation_lag, int32_t* first_negative_lag, int32_t* flags,
+                                    int max_lag_out, double* acf);
+
 /* ---- Importance sampler (is_kernels.hip) ----
  * SamplerIS::RunImpl (src/sampler/SamplerIS.cpp:49-87) in batches: draw from the prior, evaluate the
  * likelihood (bcm3hip_eval_batch_device), keep every draw whose log-weight is within 23.02585 of the
