@@ -59,12 +59,22 @@ __device__ __forceinline__ double logsum(double loga, double logb)
     return loga + log1p(exp(diff));
 }
 
+// the evaluation count of a launch: n, or the device-side count *n_dev where that is smaller
+// (bcm3hip_eval_batch_device_counted: the launch covers n_max, the items beyond *n_dev return at once)
+__device__ __forceinline__ int64_t counted_items(int64_t n, const int32_t* __restrict__ n_dev)
+{
+    if (!n_dev) return n;
+    const int64_t nd = (int64_t)*n_dev;
+    return nd < n ? nd : n;
+}
+
 __global__ void __launch_bounds__(256) banana_kernel(int64_t n, int d, double sd1, double sd2,
                                                      const double* __restrict__ values, double* __restrict__ logp,
-                                                     int32_t* __restrict__ status)
+                                                     int32_t* __restrict__ status,
+                                                    const int32_t* __restrict__ n_dev)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
+    if (e >= counted_items(n, n_dev)) return;
     const double* v = values + e * d;
     double p = 1.0;
     for (int i = 0; i < d - 1; i++) p = p * pdf_normal(v[i], 0, sd1);
@@ -77,10 +87,11 @@ __global__ void __launch_bounds__(256) banana_kernel(int64_t n, int d, double sd
 
 __global__ void __launch_bounds__(256) circular_kernel(int64_t n, int d, double radius, double offset, double width,
                                                        const double* __restrict__ values,
-                                                       double* __restrict__ logp, int32_t* __restrict__ status)
+                                                       double* __restrict__ logp, int32_t* __restrict__ status,
+                                                    const int32_t* __restrict__ n_dev)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
+    if (e >= counted_items(n, n_dev)) return;
     const double* v = values + e * d;
     double s1 = 0.0, s2 = 0.0;
     for (int i = 0; i < d; i++) {
@@ -95,10 +106,11 @@ __global__ void __launch_bounds__(256) circular_kernel(int64_t n, int d, double 
 }
 
 __global__ void __launch_bounds__(256) dummy_kernel(int64_t n, int d, const double* __restrict__ values,
-                                                    double* __restrict__ logp, int32_t* __restrict__ status)
+                                                    double* __restrict__ logp, int32_t* __restrict__ status,
+                                                    const int32_t* __restrict__ n_dev)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
+    if (e >= counted_items(n, n_dev)) return;
     logp[e] = log_pdf_tnu4(values[e * d], 0.0, 1.0);
     if (status) status[e] = 0;
 }
@@ -116,11 +128,12 @@ __global__ void __launch_bounds__(256) mixture_kernel(int64_t n, int d, int K, c
                                                       const double* __restrict__ chol,
                                                       const double* __restrict__ cst,
                                                       const double* __restrict__ values, double* __restrict__ logp,
-                                                      int32_t* __restrict__ status)
+                                                      int32_t* __restrict__ status,
+                                                    const int32_t* __restrict__ n_dev)
 {
     constexpr int DM = BCM3HIP_MIXTURE_DMAX;
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
+    if (e >= counted_items(n, n_dev)) return;
     const double* x = values + e * d;
     double xv[DM];
 #pragma unroll
@@ -167,25 +180,26 @@ __global__ void __launch_bounds__(256) mixture_kernel(int64_t n, int d, int K, c
 }
 
 hipError_t launch_analytic(const AnalyticDevModel& m, int64_t n, const double* values, double* logp,
-                           int32_t* status, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop)
+                           int32_t* status, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop,
+                           const int32_t* n_dev)
 {
     if (n == 0) return hipSuccess;
     const int tb = 256;
     dim3 grid((unsigned)((n + tb - 1) / tb)), block(tb);
     if (ev_start) hipEventRecord(ev_start, stream);
     if (m.kind == BCM3HIP_ANALYTIC_BANANA)
-        hipLaunchKernelGGL(banana_kernel, grid, block, 0, stream, n, m.d, m.p0, m.p1, values, logp, status);
+        hipLaunchKernelGGL(banana_kernel, grid, block, 0, stream, n, m.d, m.p0, m.p1, values, logp, status, n_dev);
     else if (m.kind == BCM3HIP_ANALYTIC_CIRCULAR)
         hipLaunchKernelGGL(circular_kernel, grid, block, 0, stream, n, m.d, m.p0, m.p1, m.p2, values, logp,
-                           status);
+                           status, n_dev);
     else if (m.kind == BCM3HIP_ANALYTIC_DUMMY)
-        hipLaunchKernelGGL(dummy_kernel, grid, block, 0, stream, n, m.d, values, logp, status);
+        hipLaunchKernelGGL(dummy_kernel, grid, block, 0, stream, n, m.d, values, logp, status, n_dev);
     else if (m.kind == kAnalyticMixtureBase + BCM3HIP_MIXTURE_NORMAL)
         hipLaunchKernelGGL(mixture_kernel<BCM3HIP_MIXTURE_NORMAL>, grid, block, 0, stream, n, m.d, m.K, m.mean,
-                           m.chol, m.cst, values, logp, status);
+                           m.chol, m.cst, values, logp, status, n_dev);
     else if (m.kind == kAnalyticMixtureBase + BCM3HIP_MIXTURE_T)
         hipLaunchKernelGGL(mixture_kernel<BCM3HIP_MIXTURE_T>, grid, block, 0, stream, n, m.d, m.K, m.mean, m.chol,
-                           m.cst, values, logp, status);
+                           m.cst, values, logp, status, n_dev);
     else
         return hipErrorInvalidValue;
     if (ev_stop) hipEventRecord(ev_stop, stream);

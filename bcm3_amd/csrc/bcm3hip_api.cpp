@@ -784,8 +784,13 @@ static int launch_incucyte_ctx(bcm3hip_ctx* c, size_t n, const double* dvalues, 
     return 0;
 }
 
-// the launches that take their evaluation count from device memory (n_dev): PopPK and incucyte
-static bool takes_device_count(const bcm3hip_ctx* c) { return c->kind == Kind::PopK || c->kind == Kind::Incucyte; }
+// the launches that take their evaluation count from device memory (n_dev): PopPK, incucyte,
+// cell_cycle_marker, the analytic kernels and the matrix-exponential PK kernels
+static bool takes_device_count(const bcm3hip_ctx* c)
+{
+    return c->kind == Kind::PopK || c->kind == Kind::Incucyte || c->kind == Kind::Ccm || c->kind == Kind::Analytic ||
+           c->kind == Kind::ExpmPK;
+}
 
 // scratch of the matrix-exponential path per launch: exps[n][n_jobs][n^2]; larger batches run in
 // chunks of evaluations so that it stays under this many bytes
@@ -844,7 +849,7 @@ static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp
         for (size_t i0 = 0; i0 < n && e == hipSuccess; i0 += nc) {
             const size_t m = std::min(nc, n - i0);
             e = launch_expm_pk(x, (int64_t)m, dvalues + i0 * (size_t)c->d, dlogp + i0, dstatus ? dstatus + i0 : nullptr,
-                               c->expm.exps, s, i0 == 0 ? e0 : nullptr, i0 + m >= n ? e1 : nullptr);
+                               c->expm.exps, s, i0 == 0 ? e0 : nullptr, i0 + m >= n ? e1 : nullptr, n_dev, (int64_t)i0);
         }
         break;
     }
@@ -868,10 +873,10 @@ static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp
         break;
     }
     case Kind::Ccm:
-        e = launch_ccm(c->ccm.m, (int64_t)n, dvalues, dlogp, dstatus, c->ccm.one_lane, s, e0, e1);
+        e = launch_ccm(c->ccm.m, (int64_t)n, dvalues, dlogp, dstatus, c->ccm.one_lane, s, e0, e1, n_dev);
         break;
     case Kind::Analytic:
-        e = launch_analytic(c->am, (int64_t)n, dvalues, dlogp, dstatus, s, e0, e1);
+        e = launch_analytic(c->am, (int64_t)n, dvalues, dlogp, dstatus, s, e0, e1, n_dev);
         break;
     default: return BCM3HIP_ERR_ARG;
     }

@@ -14,6 +14,7 @@ struct CcmDevModel {
 
 // one_lane: the one-lane-per-evaluation variant (BCM3HIP_OPT_CCM_ONE_LANE), same results
 hipError_t launch_ccm(const CcmDevModel& m, int64_t n, const double* values, double* logp, int32_t* status,
-                      bool one_lane, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop);
+                      bool one_lane, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop,
+                      const int32_t* n_dev = nullptr);
 
 }  // namespace bcm3hip

@@ -20,11 +20,14 @@ namespace bcm3hip {
 // workgroup = one wavefront; workgroups stride over the evaluations
 __global__ void __launch_bounds__(CCM_CHUNK) ccm_wave_kernel(CcmDevModel m, int64_t n,
                                                              const double* __restrict__ values,
-                                                             double* __restrict__ logp, int32_t* __restrict__ status)
+                                                             double* __restrict__ logp, int32_t* __restrict__ status,
+                                                             const int32_t* __restrict__ n_dev)
 {
     __shared__ double term[CCM_CHUNK];
     const int lane = threadIdx.x;
     const int64_t T = m.T;
+    // a device-side count (bcm3hip_eval_batch_device_counted): the same for every lane
+    if (n_dev && (int64_t)*n_dev < n) n = (int64_t)*n_dev;
     for (int64_t e = blockIdx.x; e < n; e += gridDim.x) {
         const CcmParams p = ccm_params(values + e * CCM_NVARS);
         double acc = 0.0;
@@ -48,16 +51,17 @@ __global__ void __launch_bounds__(CCM_CHUNK) ccm_wave_kernel(CcmDevModel m, int6
 // kept for the comparison in DESIGN.md §4 and as a second implementation the tests hold the
 // wavefront kernel against
 __global__ void __launch_bounds__(256) ccm_lane_kernel(CcmDevModel m, int64_t n, const double* __restrict__ values,
-                                                       double* __restrict__ logp, int32_t* __restrict__ status)
+                                                       double* __restrict__ logp, int32_t* __restrict__ status,
+                                                       const int32_t* __restrict__ n_dev)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
+    if (e >= n || (n_dev && e >= (int64_t)*n_dev)) return;
     logp[e] = ccm_eval_serial(values + e * CCM_NVARS, m.T, m.data);
     if (status) status[e] = BCM3HIP_STATUS_OK;
 }
 
 hipError_t launch_ccm(const CcmDevModel& m, int64_t n, const double* values, double* logp, int32_t* status,
-                      bool one_lane, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop)
+                      bool one_lane, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const int32_t* n_dev)
 {
     if (n == 0) return hipSuccess;
     const int tb = 256;
@@ -65,11 +69,11 @@ hipError_t launch_ccm(const CcmDevModel& m, int64_t n, const double* values, dou
     if (ev_start) hipEventRecord(ev_start, stream);
     if (one_lane) {
         hipLaunchKernelGGL(ccm_lane_kernel, dim3((unsigned)((n + tb - 1) / tb)), dim3(tb), 0, stream, m, n, values, logp,
-                           status);
+                           status, n_dev);
     } else {
         const int64_t max_blocks = 1 << 20;  // beyond that the workgroups stride
         hipLaunchKernelGGL(ccm_wave_kernel, dim3((unsigned)(n < max_blocks ? n : max_blocks)), dim3(CCM_CHUNK), 0, stream,
-                           m, n, values, logp, status);
+                           m, n, values, logp, status, n_dev);
     }
     const hipError_t e = hipGetLastError();
     if (ev_stop) hipEventRecord(ev_stop, stream);

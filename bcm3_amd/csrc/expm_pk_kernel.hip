@@ -339,13 +339,16 @@ __device__ void construct_matrix(const ExpmPKDevModel& m, const double* v, int j
 // recomputing them in the loop. Output: exps[e][job] column-major n x n.
 __global__ void __launch_bounds__(64) expm_pk_exp_kernel(ExpmPKDevModel m, int64_t nev,
                                                          const double* __restrict__ values,
-                                                         double* __restrict__ exps)
+                                                         double* __restrict__ exps,
+                                                         const int32_t* __restrict__ n_dev, int64_t item_base)
 {
     __shared__ ExpmShared sh;
     const int64_t b = blockIdx.x;
     const int64_t e = b / m.n_jobs;
     const int job = (int)(b - e * m.n_jobs);
-    if (e >= nev) return;  // uniform per block
+    // (uniform per block; n_dev: the device-side count of bcm3hip_eval_batch_device_counted, over the
+    // whole batch of which this launch takes the items from item_base on)
+    if (e >= nev || (n_dev && item_base + e >= (int64_t)*n_dev)) return;
     const int L = threadIdx.x;
     const int n = m.n;
     if (L == 0) {
@@ -368,14 +371,15 @@ __global__ void __launch_bounds__(64) expm_pk_exp_kernel(ExpmPKDevModel m, int64
 __global__ void __launch_bounds__(64) expm_pk_chain_kernel(ExpmPKDevModel m, int64_t nev,
                                                            const double* __restrict__ values,
                                                            const double* __restrict__ exps,
-                                                           double* __restrict__ logp, int32_t* __restrict__ status)
+                                                           double* __restrict__ logp, int32_t* __restrict__ status,
+                                                           const int32_t* __restrict__ n_dev, int64_t item_base)
 {
     __shared__ Mat A;
     __shared__ double y[NM];
     __shared__ double scal[4];
     __shared__ int fail;
     const int64_t e = blockIdx.x;
-    if (e >= nev) return;
+    if (e >= nev || (n_dev && item_base + e >= (int64_t)*n_dev)) return;
     const int j = threadIdx.x;
     const int n = m.n;
     const int nn = n * n;
@@ -473,14 +477,16 @@ hipError_t expm_prepare_device()
 }
 
 hipError_t launch_expm_pk(const ExpmPKDevModel& m, int64_t n, const double* values, double* logp, int32_t* status,
-                          double* exps, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop)
+                          double* exps, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const int32_t* n_dev,
+                          int64_t item_base)
 {
     if (n == 0) return hipSuccess;
     if (ev_start) hipEventRecord(ev_start, stream);
     if (m.n_jobs > 0)  // (none when every observation is at t = 0: the Solve loop never runs)
         hipLaunchKernelGGL(expm_pk_exp_kernel, dim3((unsigned)(n * m.n_jobs)), dim3(64), 0, stream, m, n, values,
-                           exps);
-    hipLaunchKernelGGL(expm_pk_chain_kernel, dim3((unsigned)n), dim3(64), 0, stream, m, n, values, exps, logp, status);
+                           exps, n_dev, item_base);
+    hipLaunchKernelGGL(expm_pk_chain_kernel, dim3((unsigned)n), dim3(64), 0, stream, m, n, values, exps, logp, status,
+                       n_dev, item_base);
     const hipError_t e = hipGetLastError();
     if (ev_stop) hipEventRecord(ev_stop, stream);
     return e;

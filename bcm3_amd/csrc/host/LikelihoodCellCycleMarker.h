@@ -16,6 +16,7 @@ public:
     bool Initialize(std::shared_ptr<const VariableSet> varset, const XmlNode& likelihood_node,
                     const OptionsMap& vm) override;
     bool PostInitialize() override { return true; }
+    bool SupportsCountedBatch() const override { return ctx != nullptr; }
 
     int GetTrackIndex() const { return track_ix; }
     const std::vector<Real>& GetTrack() const { return data; }

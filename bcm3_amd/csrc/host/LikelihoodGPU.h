@@ -140,6 +140,7 @@ struct PharmacoPatient {
 class PharmacoLikelihoodSingle : public LikelihoodGPUBase {
 public:
     PharmacoLikelihoodSingle(size_t sampling_threads, size_t evaluation_threads) {}
+    bool SupportsCountedBatch() const override { return ctx != nullptr; }
     bool Initialize(std::shared_ptr<const VariableSet> varset, const XmlNode& likelihood_node,
                     const OptionsMap& vm) override;
     bool PostInitialize() override;
@@ -164,6 +165,7 @@ private:
 class PharmacoLikelihoodPopulation : public LikelihoodGPUBase {
 public:
     PharmacoLikelihoodPopulation(size_t sampling_threads, size_t evaluation_threads) {}
+    bool SupportsCountedBatch() const override { return ctx != nullptr; }
     bool Initialize(std::shared_ptr<const VariableSet> varset, const XmlNode& likelihood_node,
                     const OptionsMap& vm) override;
     bool PostInitialize() override;
@@ -186,6 +188,7 @@ private:
 class TestLikelihoodBanana : public LikelihoodGPUBase {
 public:
     TestLikelihoodBanana(size_t sampling_threads, size_t evaluation_threads) {}
+    bool SupportsCountedBatch() const override { return ctx != nullptr; }
     bool Initialize(std::shared_ptr<const VariableSet> varset, const XmlNode& likelihood_node,
                     const OptionsMap& vm) override;
 
@@ -197,6 +200,7 @@ private:
 class TestLikelihoodCircular : public LikelihoodGPUBase {
 public:
     TestLikelihoodCircular(size_t sampling_threads, size_t evaluation_threads) {}
+    bool SupportsCountedBatch() const override { return ctx != nullptr; }
     bool Initialize(std::shared_ptr<const VariableSet> varset, const XmlNode& likelihood_node,
                     const OptionsMap& vm) override;
 
@@ -208,6 +212,7 @@ private:
 class TestLikelihoodMultimodalGaussians : public LikelihoodGPUBase {
 public:
     TestLikelihoodMultimodalGaussians(size_t sampling_threads, size_t evaluation_threads) {}
+    bool SupportsCountedBatch() const override { return ctx != nullptr; }
     bool Initialize(std::shared_ptr<const VariableSet> varset, const XmlNode& likelihood_node,
                     const OptionsMap& vm) override;
 };
@@ -215,6 +220,7 @@ public:
 class TestLikelihoodTruncatedT : public LikelihoodGPUBase {
 public:
     TestLikelihoodTruncatedT(size_t sampling_threads, size_t evaluation_threads) {}
+    bool SupportsCountedBatch() const override { return ctx != nullptr; }
     bool Initialize(std::shared_ptr<const VariableSet> varset, const XmlNode& likelihood_node,
                     const OptionsMap& vm) override;
 
@@ -225,6 +231,7 @@ private:
 class LikelihoodDummy : public LikelihoodGPUBase {
 public:
     LikelihoodDummy(size_t sampling_threads, size_t evaluation_threads) {}
+    bool SupportsCountedBatch() const override { return ctx != nullptr; }
     bool Initialize(std::shared_ptr<const VariableSet> varset, const XmlNode& likelihood_node,
                     const OptionsMap& vm) override;
 };

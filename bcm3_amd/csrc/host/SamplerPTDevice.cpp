@@ -875,7 +875,16 @@ struct SamplerPTDevice::Impl {
 
     // can the next two iterations run as a speculative pair (the first must not adapt: the second's
     // proposals are made before it ends)
-    bool PairPossible() const { return spec_on && !AdaptDue(cnt.samples_done, false); }
+    // ... nor may the pair's second exchange round be the start-0 round of an odd single-rank ladder:
+    // there chain 0 exchanges twice, with chain 1 and then in the wrap pair, so the last chain can
+    // receive what was chain 1's state, which is not among its candidates. Such a pair waits one
+    // iteration; the pairs after it have that round first, where it runs before anything is proposed.
+    bool PairPossible() const
+    {
+        if (!spec_on || AdaptDue(cnt.samples_done, false)) return false;
+        const bool second_round_start0 = (round + 1) % 2 == 0;
+        return !(cfg.world == 1 && Ctot % 2 == 1 && second_round_start0);
+    }
 
     // Two DeterministicEvenOdd iterations r, r+1 with ONE likelihood launch (include/bcm3hip.h
     // "speculative iteration pairs"): exchange r, propose r, the candidates of r+1 (every state

@@ -48,7 +48,8 @@ struct AnalyticDevModel {
 constexpr int32_t kAnalyticMixtureBase = 16;
 
 hipError_t launch_analytic(const AnalyticDevModel& m, int64_t n, const double* values, double* logp,
-                           int32_t* status, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop);
+                           int32_t* status, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop,
+                           const int32_t* n_dev = nullptr);
 
 // Same fields as bcm3hip_expm_pk_model, with device pointers.
 struct ExpmPKDevModel {
@@ -77,6 +78,7 @@ struct ExpmPKDevModel {
 // exps: [n][n_jobs][n*n] scratch
 hipError_t expm_prepare_device();  // expm_pk_kernel.hip: its copy of the libm tables
 hipError_t launch_expm_pk(const ExpmPKDevModel& m, int64_t n, const double* values, double* logp, int32_t* status,
-                          double* exps, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop);
+                          double* exps, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop,
+                          const int32_t* n_dev = nullptr, int64_t item_base = 0);
 
 }  // namespace bcm3hip

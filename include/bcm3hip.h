@@ -516,10 +516,12 @@ int bcm3hip_eval_batch(bcm3hip_ctx* ctx, size_t n, size_t d, const double* value
  * stream has synchronised. */
 int bcm3hip_eval_batch_device(bcm3hip_ctx* ctx, size_t n, const double* values_dev, double* logp_dev,
                               int32_t* status_dev, void* stream);
-/* PopPK only: as bcm3hip_eval_batch_device for the first *n_dev (a device int32, <= n_max) items of
+/* PopPK, incucyte, cell_cycle_marker, matrix-exponential PK and the analytic contexts (BCM3HIP_ERR_ARG
+ * for the cell-population context): as
+ * bcm3hip_eval_batch_device for the first *n_dev (a device int32, <= n_max) items of
  * values_dev, the count read on the device (the launch covers n_max; the items beyond *n_dev return
  * at once), so a batch sized by a kernel needs no host round trip; steps_dev[i] (may be NULL) =
- * BDF steps of item i's solve (one patient per evaluation; left unwritten for P > 1). SamplerPTDevice's speculative iteration pairs. */
+ * BDF steps of item i's solve (PopPK with one patient per evaluation; left unwritten otherwise). SamplerPTDevice's speculative iteration pairs. */
 int bcm3hip_eval_batch_device_counted(bcm3hip_ctx* ctx, size_t n_max, const int32_t* n_dev, const double* values_dev,
                                       double* logp_dev, int32_t* status_dev, int32_t* steps_dev, void* stream);
 int bcm3hip_last_kernel_ms(bcm3hip_ctx* ctx, float* ms);
