@@ -237,6 +237,42 @@ def column_waic(data) -> dict:
     return out
 
 
+PSIS_KEYS = ("count", "tail", "pareto_k", "elpd_loo", "n_eff")
+PSIS_INT_KEYS = ("count", "tail")
+
+
+def column_psis_loo_host(data) -> dict:
+    """bcm3hip_column_psis_loo_host: the PSIS-LOO kernel's source compiled for the host -- per column of
+    data [n, cols] of pointwise log-likelihoods (NaN = no value) count, tail (int32), pareto_k, elpd_loo,
+    n_eff [cols]. Needs no device."""
+    x = np.ascontiguousarray(data, dtype=np.float64)
+    n, cols = x.shape
+    out = {k: np.empty(cols, dtype=np.int32 if k in PSIS_INT_KEYS else np.float64) for k in PSIS_KEYS}
+    check(lib().bcm3hip_column_psis_loo_host(n, cols, x.ctypes.data, *(out[k].ctypes.data for k in PSIS_KEYS)),
+          "bcm3hip_column_psis_loo_host")
+    return out
+
+
+def column_psis_loo(data) -> dict:
+    """bcm3hip_column_psis_loo on data's device and torch's current stream: data is a CUDA float64 tensor
+    [n, cols]. Returns CUDA tensors under the keys of column_psis_loo_host; the launch is asynchronous."""
+    import torch
+    x = data.contiguous()
+    n, cols = x.shape
+    out = {k: torch.empty(cols, dtype=torch.int32 if k in PSIS_INT_KEYS else torch.float64, device=x.device)
+           for k in PSIS_KEYS}
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        check(lib().bcm3hip_column_psis_loo(n, cols, x.data_ptr(), *(out[k].data_ptr() for k in PSIS_KEYS), stream),
+              "bcm3hip_column_psis_loo")
+    return out
+
+
+def predict_obs_loo_outputs(P: int, T: int) -> dict:
+    """the outputs of bcm3hip_predict_obs_loo in argument order"""
+    return {k: np.empty((P, T), dtype=np.int32 if k in PSIS_INT_KEYS else np.float64) for k in PSIS_KEYS}
+
+
 CHAIN_KEYS = ("mean", "sd", "rho1", "ess", "decorrelation_lag", "first_negative_lag", "flags")
 CHAIN_INT_KEYS = ("decorrelation_lag", "first_negative_lag", "flags")
 CHAIN_NONFINITE, CHAIN_CONSTANT, CHAIN_NO_NEGATIVE_LAG = 1, 2, 4  # BCM3HIP_CHAIN_*
@@ -402,6 +438,14 @@ def lib() -> C.CDLL:
     L.bcm3hip_predict_obs.restype = C.c_int
     L.bcm3hip_predict_obs_last_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 4
     L.bcm3hip_predict_obs_last_ms.restype = C.c_int
+    L.bcm3hip_column_psis_loo.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.bcm3hip_column_psis_loo.restype = C.c_int
+    L.bcm3hip_column_psis_loo_host.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp]
+    L.bcm3hip_column_psis_loo_host.restype = C.c_int
+    L.bcm3hip_predict_obs_loo.argtypes = [vp] * 6
+    L.bcm3hip_predict_obs_loo.restype = C.c_int
+    L.bcm3hip_predict_obs_loo_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.bcm3hip_predict_obs_loo_last_ms.restype = C.c_int
     for f in ("bcm3hip_open_popk", "bcm3hip_open_analytic", "bcm3hip_open_mixture", "bcm3hip_open_expm_pk", "bcm3hip_close", "bcm3hip_set_option",
               "bcm3hip_num_variables", "bcm3hip_eval_batch", "bcm3hip_eval_batch_device",
               "bcm3hip_last_kernel_ms", "bcm3hip_eval_batch_detail"):
@@ -595,6 +639,21 @@ class Context:
         ms = [C.c_float() for _ in range(4)]
         check(lib().bcm3hip_predict_obs_last_ms(self.h, *(C.byref(x) for x in ms)), "bcm3hip_predict_obs_last_ms")
         return tuple(float(x.value) for x in ms)
+
+    def predict_obs_loo(self) -> dict:
+        """bcm3hip_predict_obs_loo (PopPK contexts): the PSIS-LOO terms per observation -- count, tail
+        (int32), pareto_k, elpd_loo, n_eff [P, T] -- of the pointwise log-likelihoods the last predict_obs
+        left on the device. Raises when no predict_obs result is current (none yet, or an eval / predict
+        since)."""
+        out = predict_obs_loo_outputs(self.P, self.T)
+        check(lib().bcm3hip_predict_obs_loo(self.h, *(_ptr(out[k]) for k in PSIS_KEYS)), "bcm3hip_predict_obs_loo")
+        return out
+
+    def predict_obs_loo_last_ms(self) -> float:
+        """ms of the PSIS-LOO kernel of the last predict_obs_loo, by HIP events on the context's stream"""
+        ms = C.c_float()
+        check(lib().bcm3hip_predict_obs_loo_last_ms(self.h, C.byref(ms)), "bcm3hip_predict_obs_loo_last_ms")
+        return float(ms.value)
 
     def eval_device(self, n: int, values_ptr: int, logp_ptr: int, status_ptr: Optional[int] = None,
                     stream: Optional[int] = None):

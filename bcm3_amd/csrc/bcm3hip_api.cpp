@@ -21,6 +21,7 @@
 #include "incucyte_kernel.h"
 #include "popk_kernel.h"
 #include "predict_obs.h"
+#include "psis.h"
 #include "predict_quantile.h"
 
 const xm::GlibcPow* bcm3_pow_tables(int* from_libm);  // libm_tables.cpp
@@ -99,6 +100,14 @@ struct bcm3hip_ctx {
         DevBuf<int32_t> obs_ccount, obs_pcount, obs_wcount;
         hipEvent_t obs_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         bool obs_timed = false;
+        // bcm3hip_predict_obs_loo: the PSIS-LOO terms of obs_pll ([3][P*T]: pareto_k, elpd_loo, n_eff),
+        // its event pair, and the rows of the predict_obs result obs_pll holds (0: none is current --
+        // every launch of the context resets it)
+        DevBuf<double> loo_terms;
+        DevBuf<int32_t> loo_count, loo_tail;
+        hipEvent_t loo_ev[2] = {nullptr, nullptr};
+        bool loo_timed = false;
+        size_t obs_rows = 0;
     } popk;
     AnalyticDevModel am{};
     struct {
@@ -672,6 +681,8 @@ int bcm3hip_close(bcm3hip_ctx* c)
         if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->popk.obs_ev)
         if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->popk.loo_ev)
+        if (e) hipEventDestroy(e);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return 0;
@@ -801,6 +812,7 @@ static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp
                   int32_t* dsteps = nullptr)
 {
     if ((n_dev || dsteps) && !takes_device_count(c)) return BCM3HIP_ERR_ARG;
+    c->popk.obs_rows = 0;  // whatever predict_obs left is no longer the context's last result
     hipError_t e = hipSuccess;
     if (c->scratch_used && c->scratch_stream != s) HIPCHK(hipStreamWaitEvent(s, c->scratch_ev, 0));
     hipEvent_t e0 = c->ev0, e1 = c->ev1;
@@ -1144,6 +1156,7 @@ int bcm3hip_predict_obs(bcm3hip_ctx* c, size_t n, size_t d, const double* values
     HIPCHK(hipEventRecord(b.obs_ev[1], c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     b.obs_timed = true;
+    b.obs_rows = n;
     return 0;
 }
 
@@ -1155,6 +1168,47 @@ int bcm3hip_predict_obs_last_ms(bcm3hip_ctx* c, float* obs_ms, float* quantile_m
     if (quantile_ms) HIPCHK(hipEventElapsedTime(quantile_ms, b.obs_ev[3], b.obs_ev[4]));
     if (waic_ms) HIPCHK(hipEventElapsedTime(waic_ms, b.obs_ev[4], b.obs_ev[5]));
     if (total_ms) HIPCHK(hipEventElapsedTime(total_ms, b.obs_ev[0], b.obs_ev[1]));
+    return 0;
+}
+
+int bcm3hip_predict_obs_loo(bcm3hip_ctx* c, int32_t* count, int32_t* tail, double* pareto_k, double* elpd_loo, double* n_eff)
+{
+    if (!c || c->kind != Kind::PopK || c->popk.obs_rows == 0) return BCM3HIP_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    auto& b = c->popk;
+    const size_t n = b.obs_rows, cols = (size_t)b.m.P * (size_t)b.m.T;
+    if (b.loo_terms.grow(3 * cols, kFloor) || b.loo_count.grow(cols, kFloor) || b.loo_tail.grow(cols, kFloor))
+        return BCM3HIP_ERR_ALLOC;
+    for (hipEvent_t& e : b.loo_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    b.loo_timed = false;
+    double* const t = b.loo_terms;
+    HIPCHK(hipEventRecord(b.loo_ev[0], c->stream));
+    const hipError_t e = launch_psis_loo((int64_t)n, (int64_t)cols, b.obs_pll, b.loo_count, b.loo_tail, t, t + cols,
+                                         t + 2 * cols, c->stream);
+    if (e != hipSuccess) {
+        fprintf(stderr, "bcm3hip: PSIS-LOO kernel launch failed: %s\n", hipGetErrorString(e));
+        return BCM3HIP_ERR_HIP;
+    }
+    HIPCHK(hipEventRecord(b.loo_ev[1], c->stream));
+    auto back = [&](void* dst, const void* src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    const size_t cb = cols * sizeof(double), ci = cols * sizeof(int32_t);
+    HIPCHK(back(count, b.loo_count, ci));
+    HIPCHK(back(tail, b.loo_tail, ci));
+    HIPCHK(back(pareto_k, t, cb));
+    HIPCHK(back(elpd_loo, t + cols, cb));
+    HIPCHK(back(n_eff, t + 2 * cols, cb));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    b.loo_timed = true;
+    return 0;
+}
+
+int bcm3hip_predict_obs_loo_last_ms(bcm3hip_ctx* c, float* loo_ms)
+{
+    if (!c || c->kind != Kind::PopK || !c->popk.loo_timed) return BCM3HIP_ERR_ARG;
+    if (loo_ms) HIPCHK(hipEventElapsedTime(loo_ms, c->popk.loo_ev[0], c->popk.loo_ev[1]));
     return 0;
 }
 

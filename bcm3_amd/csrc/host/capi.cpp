@@ -209,6 +209,31 @@ int bcm3_likelihood_predict_obs(bcm3_likelihood* h, size_t n, const double* valu
     return 0;
 }
 
+int bcm3_likelihood_predict_obs_loo(bcm3_likelihood* h, int32_t* count, int32_t* tail, double* pareto_k, double* elpd_loo,
+                                    double* n_eff, float* loo_ms)
+{
+    if (!h || !h->ll) return -1;
+    bcm3::LikelihoodGPUBase* p = dynamic_cast<bcm3::LikelihoodPopPKTrajectory*>(h->ll.get());
+    if (!p) p = dynamic_cast<bcm3::LikelihoodPharmacokineticTrajectory*>(h->ll.get());
+    if (!p) {
+        LOGERROR("PSIS-LOO needs a likelihood with a trajectory output (pop_pk_trajectory or "
+                 "pharmacokinetic_trajectory)");
+        return -2;
+    }
+    if (!p->Context()) {
+        LOGERROR("PSIS-LOO needs a device; the likelihood was created without one");
+        return -2;
+    }
+    int r = bcm3hip_predict_obs_loo(p->Context(), count, tail, pareto_k, elpd_loo, n_eff);
+    if (r == 0 && loo_ms) r = bcm3hip_predict_obs_loo_last_ms(p->Context(), loo_ms);
+    if (r) {
+        LOGERROR("bcm3hip_predict_obs_loo: %s (it takes the result of the likelihood's last predict_obs; an "
+                 "evaluation since then discards it)", bcm3hip_error_string(r));
+        return -3;
+    }
+    return 0;
+}
+
 int64_t bcm3_likelihood_ccm_track(const bcm3_likelihood* h, double* data, int64_t cap, int32_t* track_ix)
 {
     if (!h || !h->ll) return -1;

@@ -36,6 +36,7 @@ def lib() -> C.CDLL:
     L.bcm3_likelihood_predict.argtypes = [vp, sz, vp, C.c_int, vp, vp, vp, vp, vp]
     L.bcm3_likelihood_predict_status.argtypes = [vp, sz, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.bcm3_likelihood_predict_obs.argtypes = [vp, sz, vp, C.c_uint64, C.c_int, vp] + [vp] * 17
+    L.bcm3_likelihood_predict_obs_loo.argtypes = [vp] * 6 + [C.POINTER(C.c_float)]
     L.bcm3_likelihood_ccm_track.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int32)]
     L.bcm3_likelihood_ccm_track.restype = C.c_int64
     L.bcm3_table_read.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_int64), vp, C.c_int64]
@@ -208,6 +209,29 @@ class Likelihood:
         out["time"] = _hip.popk_time(m)
         out["observed"] = _hip.popk_observed(m)
         return out
+
+    def predict_obs_loo(self) -> dict:
+        """pop_pk_trajectory / pharmacokinetic_trajectory: the PSIS-LOO terms per observation of the last
+        predict_obs (bcm3_likelihood_predict_obs_loo; bcm3_amd.predict.measurements(loo=True) is the front
+        end), the arrays of _hip.Context.predict_obs_loo."""
+        try:
+            m = self.popk_model()
+        except RuntimeError:
+            m = None  # the library call below refuses the type with its own message
+        P, T = (int(m.P), int(m.T)) if m is not None else (0, 0)
+        out = _hip.predict_obs_loo_outputs(P, T)
+        ms = C.c_float()
+        r = lib().bcm3_likelihood_predict_obs_loo(self.h, *(out[k].ctypes.data for k in _hip.PSIS_KEYS), C.byref(ms))
+        if r != 0:
+            _err("bcm3_likelihood_predict_obs_loo", r)
+        self._loo_ms = float(ms.value)
+        return out
+
+    def predict_obs_loo_last_ms(self) -> float:
+        """ms of the PSIS-LOO kernel of the last predict_obs_loo"""
+        if getattr(self, "_loo_ms", None) is None:
+            raise RuntimeError("predict_obs_loo_last_ms: no predict_obs_loo has run on this likelihood")
+        return self._loo_ms
 
     def ccm_track(self):
         """cell_cycle_marker: (track index, the track's frames [T]) the likelihood evaluates against

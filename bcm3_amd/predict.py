@@ -160,7 +160,44 @@ def waic_totals(count, lppd, p_waic, elpd) -> dict:
                 lppd=float(np.asarray(lppd)[use].sum()), se=se, n_obs=n_obs)
 
 
-def measurements(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95), seed: int = 0, pointwise: bool = False) -> dict:
+def loo_totals(count, elpd_loo, lppd, pareto_k, k_threshold: float = 0.7) -> dict:
+    """the PSIS-LOO totals over the points waic_totals takes (count >= 2): elpd_loo, p_loo = sum (lppd_i -
+    elpd_loo_i), se = sqrt(n_obs var(elpd_loo_i)), var with denominator n_obs - 1 (NaN for fewer than two
+    points), n_obs, and n_high_k, the number of those points with pareto_k > k_threshold (an unfitted
+    point's pareto_k is +inf and counts)"""
+    use = np.asarray(count) >= 2
+    n_obs = int(use.sum())
+    e = np.asarray(elpd_loo)[use]
+    se = float(np.sqrt(n_obs * np.var(e, ddof=1))) if n_obs >= 2 else float("nan")
+    return dict(elpd_loo=float(e.sum()), p_loo=float((np.asarray(lppd)[use] - e).sum()), se=se, n_obs=n_obs,
+                n_high_k=int((np.asarray(pareto_k)[use] > k_threshold).sum()))
+
+
+def compare(a: dict, b: dict, criterion: str = "loo") -> dict:
+    """The difference of two models' measurements results on the same data: elpd_diff = sum_i (a_i - b_i)
+    of the pointwise elpd ("loo": out["loo"]["elpd"], "waic": out["waic"]["elpd"]) over the points both
+    have (count >= 2 in both), se_diff = sqrt(n_obs var(a_i - b_i)), var with denominator n_obs - 1 (NaN
+    for fewer than two points), and n_obs. Positive favours a. ValueError when the observed arrays differ
+    or a result lacks the criterion."""
+    if criterion not in ("loo", "waic"):
+        raise ValueError(f"criterion must be 'loo' or 'waic', got {criterion!r}")
+    oa, ob = np.asarray(a["observed"], dtype=np.float64), np.asarray(b["observed"], dtype=np.float64)
+    if oa.shape != ob.shape or not np.array_equal(oa, ob, equal_nan=True):
+        raise ValueError("compare: the two results were not computed on the same observations")
+    for name, r in (("first", a), ("second", b)):
+        if criterion not in r:
+            raise ValueError(f"compare: the {name} result has no {criterion!r} terms"
+                             + (" (measurements(..., loo=True))" if criterion == "loo" else ""))
+    ta, tb = a[criterion], b[criterion]
+    use = (np.asarray(ta["count"]) >= 2) & (np.asarray(tb["count"]) >= 2)
+    diff = np.asarray(ta["elpd"])[use] - np.asarray(tb["elpd"])[use]
+    n_obs = int(use.sum())
+    se = float(np.sqrt(n_obs * np.var(diff, ddof=1))) if n_obs >= 2 else float("nan")
+    return dict(elpd_diff=float(diff.sum()), se_diff=se, n_obs=n_obs)
+
+
+def measurements(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95), seed: int = 0, pointwise: bool = False,
+                 loo: bool = False, k_threshold: float = 0.7) -> dict:
     """Predicted measurements of samples [n, d] under a pop_pk_trajectory / pharmacokinetic_trajectory
     Likelihood or a PopPK Context: what can be laid over the data.
 
@@ -176,6 +213,11 @@ def measurements(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95), seed: 
                      points with count >= 2
       logp, status   [n] as evaluate_batch returns them
       pointwise=True also concentration_draws, predicted_draws, pointwise_llh [n, P, T], scales [n, 2]
+      loo=True       also loo: PSIS-LOO per observation [P, T] -- count, tail (the fitted tail length, 0:
+                     not fitted), pareto_k (+inf where not fitted), elpd, p_loo = lppd - elpd, n_eff --
+                     and the totals elpd_loo, p_loo_total, se, n_obs over the points with count >= 2,
+                     n_high_k of which have pareto_k > k_threshold: there the estimate is not to be
+                     trusted, and the model fits that measurement badly
 
     At most MAX_SAMPLES (8192) samples per call: more raises ValueError -- thin the draws first."""
     ll = likelihood_or_context
@@ -192,6 +234,14 @@ def measurements(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95), seed: 
     out["waic"] = dict(count=raw["waic_count"], lppd=raw["lppd"], mean=raw["llh_mean"], p_waic=raw["p_waic"],
                        elpd=raw["elpd"], elpd_waic=tot["elpd_waic"], p_waic_total=tot["p_waic"],
                        lppd_total=tot["lppd"], se=tot["se"], n_obs=tot["n_obs"])
+    if loo:  # on the pointwise log-likelihoods predict_obs left on the device
+        t = ll.predict_obs_loo()
+        with np.errstate(invalid="ignore"):
+            p_loo = raw["lppd"] - t["elpd_loo"]
+        tot = loo_totals(t["count"], t["elpd_loo"], raw["lppd"], t["pareto_k"], k_threshold)
+        out["loo"] = dict(count=t["count"], tail=t["tail"], pareto_k=t["pareto_k"], elpd=t["elpd_loo"], p_loo=p_loo,
+                          n_eff=t["n_eff"], elpd_loo=tot["elpd_loo"], p_loo_total=tot["p_loo"], se=tot["se"],
+                          n_obs=tot["n_obs"], n_high_k=tot["n_high_k"], k_threshold=float(k_threshold))
     if pointwise:
         out.update(concentration_draws=raw["conc"], predicted_draws=raw["ypred"], pointwise_llh=raw["pll"],
                    scales=raw["scales"])
@@ -199,7 +249,8 @@ def measurements(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95), seed: 
 
 
 def measurements_from_output(path: str, likelihood, temperature_index: int = -1, burn_in: int = 0, thin: int = 1,
-                             probs=(0.05, 0.5, 0.95), seed: int = 0, pointwise: bool = False) -> dict:
+                             probs=(0.05, 0.5, 0.95), seed: int = 0, pointwise: bool = False, loo: bool = False,
+                             k_threshold: float = 0.7) -> dict:
     """measurements on the samples of an output.nc, selected and checked as from_output does"""
     rows = select_samples(path, getattr(likelihood, "variable_names", None), temperature_index, burn_in, thin)
-    return measurements(likelihood, rows, probs, seed, pointwise)
+    return measurements(likelihood, rows, probs, seed, pointwise, loo, k_threshold)

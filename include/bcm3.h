@@ -73,6 +73,11 @@ int bcm3_likelihood_predict_obs(bcm3_likelihood* ll, size_t n, const double* val
                                 double* pred_q, double* pred_mean, int32_t* pred_count, int32_t* waic_count, double* lppd,
                                 double* llh_mean, double* p_waic, double* elpd, double* logp, int32_t* status,
                                 double* conc, double* ypred, double* pll, double* scales);
+/* The PSIS-LOO terms per observation [P][T] of the pointwise log-likelihoods the likelihood's last
+ * bcm3_likelihood_predict_obs left on the device (bcm3hip_predict_obs_loo; any array may be NULL), and
+ * the kernel's HIP-event time (may be NULL). -3 when no such result is current. */
+int bcm3_likelihood_predict_obs_loo(bcm3_likelihood* ll, int32_t* count, int32_t* tail, double* pareto_k,
+                                    double* elpd_loo, double* n_eff, float* loo_ms);
 /* cell_cycle_marker: the track the likelihood evaluates against (the row ccm.track_ix selected):
  * copies up to cap frames into data (may be NULL) and the row index into *track_ix (may be NULL);
  * returns the number of frames, -2 for other likelihood types. */

@@ -1021,6 +1021,44 @@ int bcm3hip_is_filter_host(int64_t n, int d, const double* llh, const double* va
                            double learning_rate, int64_t limit, bcm3hip_is_state* state, double* out_values,
                            double* out_lprior, double* out_llh, double* out_weight);
 
+/* ---- PSIS-LOO (psis_kernels.hip) ----
+ * Pareto-smoothed importance-sampling leave-one-out per column of a row-major data[n][cols] of pointwise
+ * log-likelihoods l_s, NaN meaning "no value" (Vehtari, Gelman & Gabry 2017; Vehtari et al. 2024; the
+ * tail fit of Zhang & Stephens 2009), with r_eff = 1:
+ *   count = S, the number of values. The log ratios r_s = -l_s are sorted ascending, lw_s = r_s - r_max.
+ *   M = min(S / 5, m), m the smallest integer with m * m >= 9 * S; the M largest lw are the tail, the
+ *   largest lw below it the cutoff c, x_i = exp(lw_i) - exp(c) (i = 1..M, ascending) the excesses.
+ *   The tail is fitted when M >= 5 and x_1 > 0: with G = 30 + floor(sqrt(M)), q = floor(M / 4 + 1 / 2),
+ *     b_j = 1 / x_M + (1 - sqrt(G / (j - 0.5))) / (3 * x_q),  k_j = mean_i log(1 - b_j * x_i),
+ *     L_j = M * (log(-b_j / k_j) - k_j - 1),  w_j = 1 / sum_l exp(L_l - L_j)          (j, l = 1..G),
+ *     b = sum_j b_j * w_j,  k = mean_i log(1 - b * x_i),  sigma = -k / b,  k <- (M * k + 5) / (M + 10);
+ *   a non-finite k or sigma, or sigma <= 0, leaves the column unfitted. A fitted tail's order statistic
+ *   i becomes min(log(exp(c) + sigma * (exp(-k * log(1 - p_i)) - 1) / k), 0), p_i = (i - 0.5) / M
+ *   (-sigma * log(1 - p_i) in place of the quotient for |k| < 1e-8).
+ *   tail = M and pareto_k = k of a fitted column; tail = 0 and pareto_k = +inf of an unfitted one, whose
+ *   weights stay raw. elpd_loo = LSE_s(lw'_s + l_s) - LSE_s(lw'_s), each log-sum-exp shifted by its
+ *   maximum; n_eff = (sum_s e_s)^2 / sum_s e_s^2, e_s = exp(lw'_s - max lw'), which is 1 / sum of the
+ *   squared normalised weights. S = 0: count = tail = 0 and NaN; a column holding +-inf: count = S, tail
+ *   = 0 and NaN. exp and log are correctly rounded; the summation orders, functions of S and M alone,
+ *   are listed in bcm3_amd/csrc/psis.h.
+ * Limits: 1 <= n <= BCM3HIP_PREDICT_MAX_N, cols >= 0, no NULL pointer when cols > 0; anything else is
+ * BCM3HIP_ERR_ARG before any launch.
+ * On device buffers, on the current device, asynchronous on `stream`. */
+int bcm3hip_column_psis_loo(int64_t n, int64_t cols, const double* data_dev, int32_t* count_dev, int32_t* tail_dev,
+                            double* k_dev, double* elpd_dev, double* neff_dev, void* stream);
+/* The same source compiled for the host (std::sort in place of the sorting network), host buffers
+ * throughout; needs no device. Bit-identical to the kernel. */
+int bcm3hip_column_psis_loo_host(int64_t n, int64_t cols, const double* data, int32_t* count, int32_t* tail, double* k,
+                                 double* elpd, double* neff);
+/* bcm3hip_column_psis_loo over the pll[n][P*T] that the context's last bcm3hip_predict_obs left on the
+ * device, on the context's stream; copies back the five arrays [P][T] (any may be NULL). Synchronous.
+ * BCM3HIP_ERR_ARG for a context without a PopPK model, and when no bcm3hip_predict_obs result is
+ * current: before the first one, and after any later evaluation or bcm3hip_predict on the context. */
+int bcm3hip_predict_obs_loo(bcm3hip_ctx* ctx, int32_t* count, int32_t* tail, double* pareto_k, double* elpd_loo,
+                            double* n_eff);
+/* HIP-event time of the kernel of the context's last bcm3hip_predict_obs_loo. */
+int bcm3hip_predict_obs_loo_last_ms(bcm3hip_ctx* ctx, float* loo_ms);
+
 #ifdef __cplusplus
 }
 #endif
