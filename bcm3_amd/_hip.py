@@ -340,6 +340,92 @@ def predict_obs_pointers(out: dict):
     return [None if v is None else v.ctypes.data for v in out.values()]
 
 
+# ---- predictive checks of the matrix-exponential PK likelihoods (flat observation axis [n_obs]) ----
+EXPM_GRID_MAX = 1024               # BCM3HIP_EXPM_GRID_MAX
+EXPM_PREDICT_MAX_BYTES = 4 << 30   # BCM3HIP_EXPM_PREDICT_MAX_BYTES
+OPT_EXPM_SCRATCH_BYTES = 8         # BCM3HIP_OPT_EXPM_SCRATCH_BYTES
+
+
+def expm_compartments(m) -> int:
+    """N of a bcm3hip_expm_pk_model (structure or dict of its fields)"""
+    g = m.get if isinstance(m, dict) else (lambda k, d=0: getattr(m, k, d))
+    return 2 + (1 if g("peripheral", 0) else 0) + (1 if g("metabolite", 0) else 0) + max(int(g("n_transit", 0)), 0)
+
+
+def expm_slots(m: ExpmPKModel) -> dict:
+    """P, N, n_obs and the slot metadata of a bcm3hip_expm_pk_model: patient (int32), time, observed [n_obs]"""
+    P, no = int(m.P), int(m.n_obs)
+    dbl = lambda p: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_double)), shape=(no,)).copy()  # noqa: E731
+    if m.obs_offset:
+        off = np.ctypeslib.as_array(C.cast(m.obs_offset, C.POINTER(C.c_int32)), shape=(P + 1,)).copy()
+    else:
+        off = np.array([0, no], dtype=np.int32)
+    patient = np.repeat(np.arange(P, dtype=np.int32), np.diff(off))
+    return dict(P=P, N=expm_compartments(m), n_obs=no, patient=patient, time=dbl(m.obs_times), observed=dbl(m.obs_conc),
+                obs_offset=off)
+
+
+def expm_jobs_host(treat_offset, treat_times, slot_offset, slot_times) -> dict:
+    """bcm3hip_expm_jobs_host: the step lengths PharmacokineticModel::Solve exponentiates for per-patient
+    doses and output slots -- job_dt, job_patient [n_jobs], interval_job [n_treat], slot_job [n_slots].
+    Needs no device."""
+    to = np.ascontiguousarray(treat_offset, dtype=np.int32)
+    so = np.ascontiguousarray(slot_offset, dtype=np.int32)
+    tt = np.ascontiguousarray(treat_times, dtype=np.float64)
+    st = np.ascontiguousarray(slot_times, dtype=np.float64)
+    P = to.size - 1
+    cap = tt.size + st.size
+    nj = C.c_int32()
+    dt, jp = np.empty(cap), np.empty(cap, dtype=np.int32)
+    ij, sj = np.empty(tt.size, dtype=np.int32), np.empty(st.size, dtype=np.int32)
+    check(lib().bcm3hip_expm_jobs_host(P, to.ctypes.data, tt.ctypes.data, so.ctypes.data, st.ctypes.data, C.byref(nj),
+                                       dt.ctypes.data, jp.ctypes.data, ij.ctypes.data, sj.ctypes.data),
+          "bcm3hip_expm_jobs_host")
+    return dict(job_dt=dt[:nj.value].copy(), job_patient=jp[:nj.value].copy(), interval_job=ij, slot_job=sj)
+
+
+def expm_predict_obs_outputs(n: int, k: int, cols: int, pointwise: bool) -> dict:
+    """the outputs of bcm3hip_expm_predict_obs in argument order"""
+    i = np.int32
+    out = dict(conc_q=np.empty((k, cols)), conc_mean=np.empty(cols), conc_count=np.empty(cols, dtype=i),
+               pred_q=np.empty((k, cols)), pred_mean=np.empty(cols), pred_count=np.empty(cols, dtype=i),
+               waic_count=np.empty(cols, dtype=i), lppd=np.empty(cols), llh_mean=np.empty(cols),
+               p_waic=np.empty(cols), elpd=np.empty(cols), logp=np.empty(n), status=np.empty(n, dtype=i))
+    for key in ("conc", "ypred", "pll"):
+        out[key] = np.empty((n, cols)) if pointwise else None
+    out["scales"] = np.empty((n, 2)) if pointwise else None
+    return out
+
+
+def expm_predict_grid_outputs(n: int, k: int, P: int, G: int, N: int, states: bool, pointwise: bool = False) -> dict:
+    """the outputs of bcm3hip_expm_predict_grid in argument order"""
+    i = np.int32
+    s = (P, G, N) if states else (0, 0, 0)
+    return dict(conc_q=np.empty((k, P, G)), conc_mean=np.empty((P, G)), conc_count=np.empty((P, G), dtype=i),
+                state_q=np.empty((k,) + s) if states else None, state_mean=np.empty(s) if states else None,
+                state_count=np.empty(s, dtype=i) if states else None, logp=np.empty(n), status=np.empty(n, dtype=i),
+                conc=np.empty((n, P, G)) if pointwise else None,
+                state=np.empty((n, P, G, N)) if pointwise and states else None)
+
+
+def expm_grid_check(n: int, P: int, N: int, times):
+    """times as an array within the limits of bcm3hip_expm_predict_grid; ValueError naming the figures"""
+    t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+    if not 1 <= t.size <= EXPM_GRID_MAX:
+        raise ValueError(f"between 1 and {EXPM_GRID_MAX} time points per call, got {t.size}")
+    if not np.all(np.isfinite(t)) or np.any(t < 0.0) or np.any(np.diff(t) < 0.0):
+        bad = int(np.flatnonzero(~np.isfinite(t) | (t < 0.0) | np.concatenate(([False], np.diff(t) < 0.0)))[0])
+        raise ValueError(f"times must be finite, >= 0 and non-decreasing; times[{bad}] = {t[bad]}")
+    if not t[-1] > 0.0:
+        raise ValueError(f"the last time point must be > 0, got {t[-1]}")
+    need = n * P * t.size * (N + 1) * 8
+    if need > EXPM_PREDICT_MAX_BYTES:
+        raise ValueError(f"{n} samples x {P} patients x {t.size} time points x {N + 1} values take {need} bytes of "
+                         f"trajectories on the device, more than the {EXPM_PREDICT_MAX_BYTES} allowed; thin the draws "
+                         f"or the grid")
+    return t
+
+
 STATS_DTYPE = np.dtype([(k, np.int32) for k in ("nst", "nfe", "nni", "nsetups", "nje", "netf", "ncfn", "nreinit")])
 
 _lib = None
@@ -446,6 +532,18 @@ def lib() -> C.CDLL:
     L.bcm3hip_predict_obs_loo.restype = C.c_int
     L.bcm3hip_predict_obs_loo_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.bcm3hip_predict_obs_loo_last_ms.restype = C.c_int
+    fp = C.POINTER(C.c_float)
+    L.bcm3hip_expm_jobs_host.argtypes = [C.c_int, vp, vp, vp, vp, C.POINTER(C.c_int32), vp, vp, vp, vp]
+    L.bcm3hip_expm_predict_obs.argtypes = [vp, sz, sz, vp, C.c_uint64, C.c_int, vp] + [vp] * 17
+    L.bcm3hip_expm_predict_obs_last_ms.argtypes = [vp] + [fp] * 4
+    L.bcm3hip_expm_predict_obs_loo.argtypes = [vp] * 6
+    L.bcm3hip_expm_predict_obs_loo_last_ms.argtypes = [vp, fp]
+    L.bcm3hip_expm_predict_grid.argtypes = [vp, sz, sz, vp, C.c_int, vp, C.c_int, C.c_int, vp] + [vp] * 10
+    L.bcm3hip_expm_predict_grid_last_ms.argtypes = [vp] + [fp] * 4
+    for f in ("bcm3hip_expm_jobs_host", "bcm3hip_expm_predict_obs", "bcm3hip_expm_predict_obs_last_ms",
+              "bcm3hip_expm_predict_obs_loo", "bcm3hip_expm_predict_obs_loo_last_ms", "bcm3hip_expm_predict_grid",
+              "bcm3hip_expm_predict_grid_last_ms"):
+        getattr(L, f).restype = C.c_int
     for f in ("bcm3hip_open_popk", "bcm3hip_open_analytic", "bcm3hip_open_mixture", "bcm3hip_open_expm_pk", "bcm3hip_close", "bcm3hip_set_option",
               "bcm3hip_num_variables", "bcm3hip_eval_batch", "bcm3hip_eval_batch_device",
               "bcm3hip_last_kernel_ms", "bcm3hip_eval_batch_detail"):
@@ -570,7 +668,21 @@ class Context:
                 setattr(m, name, v)
         h = C.c_void_p()
         check(lib().bcm3hip_open_expm_pk(device, C.byref(m), C.byref(h)), "bcm3hip_open_expm_pk")
-        return cls(h, int(m.d))
+        ctx = cls(h, int(m.d))
+        ctx._set_expm_slots(expm_slots(m))
+        return ctx
+
+    def _set_expm_slots(self, s: dict):
+        """matrix-exponential PK contexts: P patients, N compartments, the flat observation axis n_obs with
+        patient (int32), time, observed [n_obs]; is_expm_pk marks the family for bcm3_amd.predict"""
+        self.is_expm_pk = True
+        self._expm_slots = s
+        self.P, self.N, self.n_obs = s["P"], s["N"], s["n_obs"]
+        self.patient, self.time, self.observed = s["patient"], s["time"], s["observed"]
+
+    def expm_slots(self) -> dict:
+        """matrix-exponential PK contexts: P, N, n_obs, patient, time, observed, obs_offset"""
+        return self._expm_slots
 
     @classmethod
     def cell_cycle_marker(cls, data, device: int = 0) -> "Context":
@@ -654,6 +766,64 @@ class Context:
         ms = C.c_float()
         check(lib().bcm3hip_predict_obs_loo_last_ms(self.h, C.byref(ms)), "bcm3hip_predict_obs_loo_last_ms")
         return float(ms.value)
+
+    def expm_predict_obs(self, values: np.ndarray, probs, seed: int = 0, pointwise: bool = False) -> dict:
+        """bcm3hip_expm_predict_obs (matrix-exponential PK contexts): predict_obs on the flat observation
+        axis -- conc_q, pred_q [n_probs, n_obs], their _mean and _count, the WAIC terms [n_obs], logp, status
+        [n]; with pointwise also conc, ypred, pll [n, n_obs] and scales [n, 2]."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        out = expm_predict_obs_outputs(n, p.size, getattr(self, "n_obs", 0), pointwise)
+        check(lib().bcm3hip_expm_predict_obs(self.h, n, self.d, _ptr(v), int(seed) & (2**64 - 1), p.size, _ptr(p),
+                                             *predict_obs_pointers(out)), "bcm3hip_expm_predict_obs")
+        return {k: a for k, a in out.items() if a is not None}
+
+    def expm_predict_obs_last_ms(self):
+        """(predict kernel, quantile launches, WAIC kernel, whole call) ms of the last expm_predict_obs"""
+        ms = [C.c_float() for _ in range(4)]
+        check(lib().bcm3hip_expm_predict_obs_last_ms(self.h, *(C.byref(x) for x in ms)),
+              "bcm3hip_expm_predict_obs_last_ms")
+        return tuple(float(x.value) for x in ms)
+
+    def expm_predict_obs_loo(self) -> dict:
+        """bcm3hip_expm_predict_obs_loo: the PSIS-LOO terms [n_obs] of the pointwise log-likelihoods the last
+        expm_predict_obs left on the device. Raises when no such result is current."""
+        cols = getattr(self, "n_obs", 0)
+        out = {k: np.empty(cols, dtype=np.int32 if k in PSIS_INT_KEYS else np.float64) for k in PSIS_KEYS}
+        check(lib().bcm3hip_expm_predict_obs_loo(self.h, *(_ptr(out[k]) for k in PSIS_KEYS)),
+              "bcm3hip_expm_predict_obs_loo")
+        return out
+
+    def expm_predict_obs_loo_last_ms(self) -> float:
+        ms = C.c_float()
+        check(lib().bcm3hip_expm_predict_obs_loo_last_ms(self.h, C.byref(ms)), "bcm3hip_expm_predict_obs_loo_last_ms")
+        return float(ms.value)
+
+    def expm_predict_grid(self, values: np.ndarray, probs, times, states: bool = False, pointwise: bool = False) -> dict:
+        """bcm3hip_expm_predict_grid: every patient simulated at times [G] -- conc_q [n_probs, P, G], conc_mean,
+        conc_count [P, G]; with states state_q [n_probs, P, G, N], state_mean, state_count; logp, status [n].
+        pointwise (tests) also returns the trajectories conc [n, P, G] and state [n, P, G, N]."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        # (another kind of context has no slots: the library refuses it)
+        P, N = (self.P, self.N) if getattr(self, "is_expm_pk", False) else (0, 0)
+        out = expm_predict_grid_outputs(n, p.size, P, t.size, N, states, pointwise)
+        check(lib().bcm3hip_expm_predict_grid(self.h, n, self.d, _ptr(v), t.size, _ptr(t), int(bool(states)), p.size,
+                                              _ptr(p), *predict_obs_pointers(out)), "bcm3hip_expm_predict_grid")
+        out = {k: a for k, a in out.items() if a is not None}
+        out["time"] = t
+        return out
+
+    def expm_predict_grid_last_ms(self):
+        """(the grid's exponentials, predict kernel, quantile launches, whole call) ms of the last
+        expm_predict_grid"""
+        ms = [C.c_float() for _ in range(4)]
+        check(lib().bcm3hip_expm_predict_grid_last_ms(self.h, *(C.byref(x) for x in ms)),
+              "bcm3hip_expm_predict_grid_last_ms")
+        return tuple(float(x.value) for x in ms)
 
     def eval_device(self, n: int, values_ptr: int, logp_ptr: int, status_ptr: Optional[int] = None,
                     stream: Optional[int] = None):

@@ -113,6 +113,36 @@ struct bcm3hip_ctx {
     struct {
         ExpmPKDevModel m{};
         DevBuf<double> exps;  // [n][n_jobs][n*n]
+        size_t scratch_bytes = 0;  // BCM3HIP_OPT_EXPM_SCRATCH_BYTES (0: kExpmScratchBytes)
+        // the host's copy of the schedule, for the job tables of a time grid
+        std::vector<int32_t> treat_offset;
+        std::vector<double> treat_times;
+        // bcm3hip_expm_predict_obs: conc, ypred, pll [n][n_obs] and scales [n][2]; the bands of conc and
+        // ypred; the WAIC terms of pll ([4][n_obs]); the request the launch's chunk loop serves (seed and
+        // event pairs around each chunk's predict kernel) and the call's other events (whole call,
+        // quantile launches, WAIC kernel); the rows of pll that are the context's current result
+        DevBuf<double> obs_conc, obs_ypred, obs_pll, obs_scales, obs_cq, obs_cmean, obs_pq, obs_pmean, obs_waic;
+        DevBuf<int32_t> obs_ccount, obs_pcount, obs_wcount;
+        bool obs_request = false;
+        uint64_t obs_seed = 0;
+        std::vector<hipEvent_t> kernel_ev;  // pairs, one per chunk
+        size_t kernel_ev_used = 0;          // pairs of the last call
+        hipEvent_t obs_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        bool obs_timed = false;
+        size_t obs_rows = 0;
+        DevBuf<double> loo_terms;
+        DevBuf<int32_t> loo_count, loo_tail;
+        hipEvent_t loo_ev[2] = {nullptr, nullptr};
+        bool loo_timed = false;
+        // bcm3hip_expm_predict_grid: the grid's job and slot tables, its trajectories conc [n][P*G] and
+        // state [n][P*G][N], their bands, and its events: the whole call and the quantile launches, and
+        // per chunk a triple around the exponentials and the predict kernel, summed by the accessor
+        DevBuf<double> grid_job_dt, grid_times, grid_conc, grid_state, grid_cq, grid_cmean, grid_sq, grid_smean;
+        DevBuf<int32_t> grid_job_patient, grid_interval_job, grid_slot_job, grid_offset, grid_ccount, grid_scount;
+        hipEvent_t grid_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        std::vector<hipEvent_t> grid_chunk_ev;  // triples per chunk: before exps, between, after predict
+        size_t grid_chunks = 0;
+        bool grid_timed = false;
     } expm;
     struct {
         bcm3hip::CellPopDev* first = nullptr;
@@ -419,6 +449,67 @@ int bcm3hip_cellpop_cells(bcm3hip_ctx* c, size_t item, int32_t* count, bcm3hip_c
     return bcm3hip::cellpop_cells(c->cp.first, item, count, records, values, end_y);
 }
 
+// The step lengths PharmacokineticModel::Solve (.cpp:127-174) will exponentiate, per patient, by the
+// loop's own arithmetic; equal values of one patient share one job. toff / soff [P+1]: patient j's
+// doses tt[toff[j], toff[j+1]) and output slots st[soff[j], soff[j+1]) (observation times, or a time
+// grid); the solve runs until the patient's last slot.
+static void expm_enumerate_jobs(int P, const int32_t* toff, const double* treat_times, const int32_t* soff,
+                                const double* slot_times, std::vector<double>& job_dt, std::vector<int32_t>& job_patient,
+                                std::vector<int32_t>& interval_job, std::vector<int32_t>& slot_job)
+{
+    job_dt.clear();
+    job_patient.clear();
+    interval_job.assign((size_t)toff[P], -1);
+    slot_job.assign((size_t)soff[P], -1);
+    for (int j = 0; j < P; j++) {
+        const size_t first = job_dt.size();
+        auto job = [&](double dt) -> int32_t {
+            for (size_t k = first; k < job_dt.size(); k++)
+                if (job_dt[k] == dt) return (int32_t)k;
+            job_dt.push_back(dt);
+            job_patient.push_back(j);
+            return (int32_t)(job_dt.size() - 1);
+        };
+        const double* tt = treat_times + toff[j];
+        const double* ot = slot_times + soff[j];
+        const int nt = toff[j + 1] - toff[j], no = soff[j + 1] - soff[j];
+        const double until = ot[no - 1];
+        int tti = 0, oti = 0;
+        double cur = 0.0;
+        while (tti < nt && cur < until) {
+            const double target = (tti < nt - 1) ? tt[tti + 1] : until;
+            while (oti < no && ot[oti] <= target) {
+                slot_job[soff[j] + oti] = job(ot[oti] - cur);
+                oti++;
+            }
+            interval_job[toff[j] + tti] = job(target - cur);
+            cur = target;
+            tti++;
+        }
+    }
+}
+
+int bcm3hip_expm_jobs_host(int P, const int32_t* treat_offset, const double* treat_times, const int32_t* slot_offset,
+                           const double* slot_times, int32_t* n_jobs, double* job_dt, int32_t* job_patient,
+                           int32_t* interval_job, int32_t* slot_job)
+{
+    if (P < 1 || !treat_offset || !treat_times || !slot_offset || !slot_times || !n_jobs || !job_dt || !job_patient ||
+        !interval_job || !slot_job)
+        return BCM3HIP_ERR_ARG;
+    if (treat_offset[0] != 0 || slot_offset[0] != 0) return BCM3HIP_ERR_ARG;
+    for (int j = 0; j < P; j++)
+        if (treat_offset[j + 1] - treat_offset[j] < 1 || slot_offset[j + 1] - slot_offset[j] < 1) return BCM3HIP_ERR_ARG;
+    std::vector<double> dt;
+    std::vector<int32_t> jp, ij, sj;
+    expm_enumerate_jobs(P, treat_offset, treat_times, slot_offset, slot_times, dt, jp, ij, sj);
+    *n_jobs = (int32_t)dt.size();
+    std::copy(dt.begin(), dt.end(), job_dt);
+    std::copy(jp.begin(), jp.end(), job_patient);
+    std::copy(ij.begin(), ij.end(), interval_job);
+    std::copy(sj.begin(), sj.end(), slot_job);
+    return 0;
+}
+
 int bcm3hip_open_expm_pk(int device, const bcm3hip_expm_pk_model* m, bcm3hip_ctx** out)
 {
     if (!m || !out) return BCM3HIP_ERR_ARG;
@@ -505,37 +596,13 @@ int bcm3hip_open_expm_pk(int device, const bcm3hip_expm_pk_model* m, bcm3hip_ctx
     x.param_map = m->param_map;
     x.P = P;
     for (int w = 0; w < 5; w++) x.sigma_ix[w] = single ? -1 : m->sigma_ix[w];
-    // the step lengths PharmacokineticModel::Solve (.cpp:127-174) will exponentiate, per patient,
-    // by the loop's own arithmetic; equal values share one job
     std::vector<double> job_dt;
-    std::vector<int32_t> job_patient, interval_job(m->n_treat, -1), obs_job(m->n_obs, -1);
-    for (int j = 0; j < P; j++) {
-        const size_t first = job_dt.size();
-        auto job = [&](double dt) -> int32_t {
-            for (size_t k = first; k < job_dt.size(); k++)
-                if (job_dt[k] == dt) return (int32_t)k;
-            job_dt.push_back(dt);
-            job_patient.push_back(j);
-            return (int32_t)(job_dt.size() - 1);
-        };
-        const double* tt = m->treat_times + toff[j];
-        const double* ot = m->obs_times + ooff[j];
-        const int nt = toff[j + 1] - toff[j], no = ooff[j + 1] - ooff[j];
-        const double until = ot[no - 1];
-        int tti = 0, oti = 0;
-        double cur = 0.0;
-        while (tti < nt && cur < until) {
-            const double target = (tti < nt - 1) ? tt[tti + 1] : until;
-            while (oti < no && ot[oti] <= target) {
-                obs_job[ooff[j] + oti] = job(ot[oti] - cur);
-                oti++;
-            }
-            interval_job[toff[j] + tti] = job(target - cur);
-            cur = target;
-            tti++;
-        }
-    }
+    std::vector<int32_t> job_patient, interval_job, obs_job;
+    expm_enumerate_jobs(P, toff.data(), m->treat_times, ooff.data(), m->obs_times, job_dt, job_patient, interval_job,
+                        obs_job);
     x.n_jobs = (int32_t)job_dt.size();
+    c->expm.treat_offset = toff;
+    c->expm.treat_times.assign(m->treat_times, m->treat_times + m->n_treat);
     if ((r = ma.upload(job_dt.data(), job_dt.size(), &x.job_dt)) ||
         (r = ma.upload(job_patient.data(), job_patient.size(), &x.job_patient)) ||
         (r = ma.upload(interval_job.data(), interval_job.size(), &x.interval_job)) ||
@@ -683,6 +750,14 @@ int bcm3hip_close(bcm3hip_ctx* c)
         if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->popk.loo_ev)
         if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->expm.kernel_ev) hipEventDestroy(e);
+    for (hipEvent_t e : c->expm.grid_chunk_ev) hipEventDestroy(e);
+    for (hipEvent_t e : c->expm.obs_ev)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->expm.loo_ev)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->expm.grid_ev)
+        if (e) hipEventDestroy(e);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return 0;
@@ -720,6 +795,10 @@ int bcm3hip_set_option(bcm3hip_ctx* c, int option, int64_t value)
     case BCM3HIP_OPT_CCM_ONE_LANE:
         if (c->kind != Kind::Ccm || (value != 0 && value != 1)) return BCM3HIP_ERR_ARG;
         c->ccm.one_lane = value != 0;
+        return 0;
+    case BCM3HIP_OPT_EXPM_SCRATCH_BYTES:
+        if (c->kind != Kind::ExpmPK || value < 0) return BCM3HIP_ERR_ARG;
+        c->expm.scratch_bytes = (size_t)value;
         return 0;
     default: return BCM3HIP_ERR_ARG;
     }
@@ -807,12 +886,20 @@ static bool takes_device_count(const bcm3hip_ctx* c)
 // chunks of evaluations so that it stays under this many bytes
 static const size_t kExpmScratchBytes = (size_t)1 << 30;
 
+// evaluations per chunk of a launch whose exponentials take per_eval doubles each
+static size_t expm_chunk(const bcm3hip_ctx* c, size_t per_eval, size_t n)
+{
+    const size_t cap = c->expm.scratch_bytes ? c->expm.scratch_bytes : kExpmScratchBytes;
+    return per_eval == 0 ? std::max<size_t>(n, 1) : std::max<size_t>(1, cap / (per_eval * sizeof(double)));
+}
+
 static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp, int32_t* dstatus,
                   double* dtraj, bcm3hip_traj_stats* dstats, hipStream_t s, const int32_t* n_dev = nullptr,
                   int32_t* dsteps = nullptr)
 {
     if ((n_dev || dsteps) && !takes_device_count(c)) return BCM3HIP_ERR_ARG;
     c->popk.obs_rows = 0;  // whatever predict_obs left is no longer the context's last result
+    c->expm.obs_rows = 0;
     hipError_t e = hipSuccess;
     if (c->scratch_used && c->scratch_stream != s) HIPCHK(hipStreamWaitEvent(s, c->scratch_ev, 0));
     hipEvent_t e0 = c->ev0, e1 = c->ev1;
@@ -855,13 +942,29 @@ static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp
     case Kind::ExpmPK: {
         const ExpmPKDevModel& x = c->expm.m;
         const size_t per_eval = (size_t)x.n_jobs * (size_t)(x.n * x.n);
-        const size_t chunk = per_eval == 0 ? n : std::max<size_t>(1, kExpmScratchBytes / (per_eval * sizeof(double)));
+        const size_t chunk = expm_chunk(c, per_eval, n);
         const size_t nc = std::min(n, chunk);
         if (c->expm.exps.grow(std::max<size_t>(nc * per_eval, 1), kFloor)) return BCM3HIP_ERR_ALLOC;
+        auto& b = c->expm;
+        b.kernel_ev_used = 0;
         for (size_t i0 = 0; i0 < n && e == hipSuccess; i0 += nc) {
             const size_t m = std::min(nc, n - i0);
             e = launch_expm_pk(x, (int64_t)m, dvalues + i0 * (size_t)c->d, dlogp + i0, dstatus ? dstatus + i0 : nullptr,
                                c->expm.exps, s, i0 == 0 ? e0 : nullptr, i0 + m >= n ? e1 : nullptr, n_dev, (int64_t)i0);
+            // bcm3hip_expm_predict_obs: the predict kernel on this chunk's exponentials, into the
+            // chunk's rows of the full buffers
+            if (b.obs_request && e == hipSuccess) {
+                while (b.kernel_ev.size() < 2 * (b.kernel_ev_used + 1)) {
+                    hipEvent_t ev;
+                    HIPCHK(hipEventCreate(&ev));
+                    b.kernel_ev.push_back(ev);
+                }
+                HIPCHK(hipEventRecord(b.kernel_ev[2 * b.kernel_ev_used], s));
+                e = launch_expm_pk_predict(x, (int64_t)m, (int64_t)i0, dvalues, b.exps, b.obs_seed, b.obs_conc, nullptr,
+                                           b.obs_pll, b.obs_ypred, b.obs_scales, s);
+                HIPCHK(hipEventRecord(b.kernel_ev[2 * b.kernel_ev_used + 1], s));
+                b.kernel_ev_used++;
+            }
         }
         break;
     }
@@ -1209,6 +1312,293 @@ int bcm3hip_predict_obs_loo_last_ms(bcm3hip_ctx* c, float* loo_ms)
 {
     if (!c || c->kind != Kind::PopK || !c->popk.loo_timed) return BCM3HIP_ERR_ARG;
     if (loo_ms) HIPCHK(hipEventElapsedTime(loo_ms, c->popk.loo_ev[0], c->popk.loo_ev[1]));
+    return 0;
+}
+
+// ---- predictive checks of the matrix-exponential PK contexts ----
+
+// n, n_probs and probs within the limits of the column reductions; probs into pr
+static bool predict_args_ok(size_t n, int n_probs, const double* probs, PredictProbs& pr)
+{
+    if (n < 1 || n > (size_t)PREDICT_MAX_N || n_probs < 1 || n_probs > PREDICT_MAX_PROBS || !probs) return false;
+    for (int k = 0; k < n_probs; k++) {
+        if (!(probs[k] >= 0.0 && probs[k] <= 1.0)) return false;
+        pr.p[k] = probs[k];
+    }
+    return true;
+}
+
+int bcm3hip_expm_predict_obs(bcm3hip_ctx* c, size_t n, size_t d, const double* values, uint64_t seed, int n_probs,
+                             const double* probs, double* conc_q, double* conc_mean, int32_t* conc_count, double* pred_q,
+                             double* pred_mean, int32_t* pred_count, int32_t* waic_count, double* lppd, double* llh_mean,
+                             double* p_waic, double* elpd, double* logp, int32_t* status, double* conc, double* ypred,
+                             double* pll, double* scales)
+{
+    if (!c || c->kind != Kind::ExpmPK || (int)d != c->d || !values || !conc_q || !pred_q || !logp) return BCM3HIP_ERR_ARG;
+    PredictProbs pr{};
+    if (!predict_args_ok(n, n_probs, probs, pr)) return BCM3HIP_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    auto& b = c->expm;
+    const size_t cols = (size_t)b.m.n_obs;  // conc, ypred, pll [n][n_obs] as data[n][cols]
+    const size_t nq = (size_t)n_probs * cols;
+    if (b.obs_conc.grow(n * cols, kFloor) || b.obs_ypred.grow(n * cols, kFloor) || b.obs_pll.grow(n * cols, kFloor) ||
+        b.obs_scales.grow(2 * n, kFloor) || b.obs_cq.grow(nq, kFloor) || b.obs_pq.grow(nq, kFloor) ||
+        b.obs_cmean.grow(cols, kFloor) || b.obs_pmean.grow(cols, kFloor) || b.obs_waic.grow(4 * cols, kFloor) ||
+        b.obs_ccount.grow(cols, kFloor) || b.obs_pcount.grow(cols, kFloor) || b.obs_wcount.grow(cols, kFloor))
+        return BCM3HIP_ERR_ALLOC;
+    for (hipEvent_t& e : b.obs_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    b.obs_timed = false;
+    HIPCHK(hipEventRecord(b.obs_ev[0], c->stream));
+    int r = stage_batch(c, n, d, values);
+    if (r) return r;
+    b.obs_request = true;
+    b.obs_seed = seed;
+    r = launch(c, n, c->values, c->logp, c->status, nullptr, nullptr, c->stream);
+    b.obs_request = false;
+    if (r) return r;
+    double* const w = b.obs_waic;
+    HIPCHK(hipEventRecord(b.obs_ev[2], c->stream));
+    hipError_t e = launch_predict_quantiles((int64_t)n, (int64_t)cols, b.obs_conc, n_probs, pr, b.obs_cq, b.obs_cmean,
+                                            b.obs_ccount, c->stream);
+    if (e == hipSuccess)
+        e = launch_predict_quantiles((int64_t)n, (int64_t)cols, b.obs_ypred, n_probs, pr, b.obs_pq, b.obs_pmean,
+                                     b.obs_pcount, c->stream);
+    HIPCHK(hipEventRecord(b.obs_ev[3], c->stream));
+    if (e == hipSuccess)
+        e = launch_predict_waic((int64_t)n, (int64_t)cols, b.obs_pll, b.obs_wcount, w, w + cols, w + 2 * cols, w + 3 * cols,
+                                c->stream);
+    HIPCHK(hipEventRecord(b.obs_ev[4], c->stream));
+    if (e != hipSuccess) {
+        fprintf(stderr, "bcm3hip: predictive-check kernel launch failed: %s\n", hipGetErrorString(e));
+        return BCM3HIP_ERR_HIP;
+    }
+    auto back = [&](void* dst, const void* src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    const size_t cb = cols * sizeof(double), ci = cols * sizeof(int32_t), full = n * cols * sizeof(double);
+    HIPCHK(back(logp, c->logp, n * sizeof(double)));
+    HIPCHK(back(status, c->status, n * sizeof(int32_t)));
+    HIPCHK(back(conc_q, b.obs_cq, nq * sizeof(double)));
+    HIPCHK(back(conc_mean, b.obs_cmean, cb));
+    HIPCHK(back(conc_count, b.obs_ccount, ci));
+    HIPCHK(back(pred_q, b.obs_pq, nq * sizeof(double)));
+    HIPCHK(back(pred_mean, b.obs_pmean, cb));
+    HIPCHK(back(pred_count, b.obs_pcount, ci));
+    HIPCHK(back(waic_count, b.obs_wcount, ci));
+    HIPCHK(back(lppd, w, cb));
+    HIPCHK(back(llh_mean, w + cols, cb));
+    HIPCHK(back(p_waic, w + 2 * cols, cb));
+    HIPCHK(back(elpd, w + 3 * cols, cb));
+    HIPCHK(back(conc, b.obs_conc, full));
+    HIPCHK(back(ypred, b.obs_ypred, full));
+    HIPCHK(back(pll, b.obs_pll, full));
+    HIPCHK(back(scales, b.obs_scales, 2 * n * sizeof(double)));
+    HIPCHK(hipEventRecord(b.obs_ev[1], c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    b.obs_timed = true;
+    b.obs_rows = n;
+    return 0;
+}
+
+int bcm3hip_expm_predict_obs_last_ms(bcm3hip_ctx* c, float* kernel_ms, float* quantile_ms, float* waic_ms, float* total_ms)
+{
+    if (!c || c->kind != Kind::ExpmPK || !c->expm.obs_timed) return BCM3HIP_ERR_ARG;
+    auto& b = c->expm;
+    if (kernel_ms) {
+        *kernel_ms = 0.0f;
+        for (size_t k = 0; k < b.kernel_ev_used; k++) {
+            float ms = 0.0f;
+            HIPCHK(hipEventElapsedTime(&ms, b.kernel_ev[2 * k], b.kernel_ev[2 * k + 1]));
+            *kernel_ms += ms;
+        }
+    }
+    if (quantile_ms) HIPCHK(hipEventElapsedTime(quantile_ms, b.obs_ev[2], b.obs_ev[3]));
+    if (waic_ms) HIPCHK(hipEventElapsedTime(waic_ms, b.obs_ev[3], b.obs_ev[4]));
+    if (total_ms) HIPCHK(hipEventElapsedTime(total_ms, b.obs_ev[0], b.obs_ev[1]));
+    return 0;
+}
+
+int bcm3hip_expm_predict_obs_loo(bcm3hip_ctx* c, int32_t* count, int32_t* tail, double* pareto_k, double* elpd_loo,
+                                 double* n_eff)
+{
+    if (!c || c->kind != Kind::ExpmPK || c->expm.obs_rows == 0) return BCM3HIP_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    auto& b = c->expm;
+    const size_t n = b.obs_rows, cols = (size_t)b.m.n_obs;
+    if (b.loo_terms.grow(3 * cols, kFloor) || b.loo_count.grow(cols, kFloor) || b.loo_tail.grow(cols, kFloor))
+        return BCM3HIP_ERR_ALLOC;
+    for (hipEvent_t& e : b.loo_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    b.loo_timed = false;
+    double* const t = b.loo_terms;
+    HIPCHK(hipEventRecord(b.loo_ev[0], c->stream));
+    const hipError_t e = launch_psis_loo((int64_t)n, (int64_t)cols, b.obs_pll, b.loo_count, b.loo_tail, t, t + cols,
+                                         t + 2 * cols, c->stream);
+    if (e != hipSuccess) {
+        fprintf(stderr, "bcm3hip: PSIS-LOO kernel launch failed: %s\n", hipGetErrorString(e));
+        return BCM3HIP_ERR_HIP;
+    }
+    HIPCHK(hipEventRecord(b.loo_ev[1], c->stream));
+    auto back = [&](void* dst, const void* src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    const size_t cb = cols * sizeof(double), ci = cols * sizeof(int32_t);
+    HIPCHK(back(count, b.loo_count, ci));
+    HIPCHK(back(tail, b.loo_tail, ci));
+    HIPCHK(back(pareto_k, t, cb));
+    HIPCHK(back(elpd_loo, t + cols, cb));
+    HIPCHK(back(n_eff, t + 2 * cols, cb));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    b.loo_timed = true;
+    return 0;
+}
+
+int bcm3hip_expm_predict_obs_loo_last_ms(bcm3hip_ctx* c, float* loo_ms)
+{
+    if (!c || c->kind != Kind::ExpmPK || !c->expm.loo_timed) return BCM3HIP_ERR_ARG;
+    if (loo_ms) HIPCHK(hipEventElapsedTime(loo_ms, c->expm.loo_ev[0], c->expm.loo_ev[1]));
+    return 0;
+}
+
+int bcm3hip_expm_predict_grid(bcm3hip_ctx* c, size_t n, size_t d, const double* values, int G, const double* times,
+                              int want_states, int n_probs, const double* probs, double* conc_q, double* conc_mean,
+                              int32_t* conc_count, double* state_q, double* state_mean, int32_t* state_count,
+                              double* logp, int32_t* status, double* conc_draws, double* state_draws)
+{
+    if (!c || c->kind != Kind::ExpmPK || (int)d != c->d || !values || !times || !conc_q || !logp) return BCM3HIP_ERR_ARG;
+    if ((want_states && !state_q) || (!want_states && state_draws)) return BCM3HIP_ERR_ARG;
+    PredictProbs pr{};
+    if (!predict_args_ok(n, n_probs, probs, pr)) return BCM3HIP_ERR_ARG;
+    if (G < 1 || G > BCM3HIP_EXPM_GRID_MAX) return BCM3HIP_ERR_ARG;
+    for (int g = 0; g < G; g++)
+        if (!std::isfinite(times[g]) || times[g] < 0.0 || (g > 0 && times[g] < times[g - 1])) return BCM3HIP_ERR_ARG;
+    if (!(times[G - 1] > 0.0)) return BCM3HIP_ERR_ARG;
+    auto& b = c->expm;
+    const size_t P = (size_t)b.m.P, N = (size_t)b.m.n;
+    const size_t cols = P * (size_t)G, scols = cols * N;
+    // n <= 8192, P * G * (N + 1) < 2^31 * 2^10 * 2^5: no overflow
+    if ((uint64_t)n * cols * (N + 1) * sizeof(double) > BCM3HIP_EXPM_PREDICT_MAX_BYTES) return BCM3HIP_ERR_ARG;
+    // the grid as every patient's slots, and the step lengths of that solve
+    std::vector<int32_t> goff(P + 1), job_patient, interval_job, slot_job;
+    std::vector<double> gt(cols), job_dt;
+    for (size_t j = 0; j <= P; j++) goff[j] = (int32_t)(j * (size_t)G);
+    for (size_t j = 0; j < P; j++) std::copy(times, times + G, gt.begin() + j * (size_t)G);
+    expm_enumerate_jobs((int)P, b.treat_offset.data(), b.treat_times.data(), goff.data(), gt.data(), job_dt, job_patient,
+                        interval_job, slot_job);
+    HIPCHK(hipSetDevice(c->device));
+    const size_t nj = job_dt.size(), per_eval = nj * N * N;
+    const size_t nc = std::min(n, expm_chunk(c, per_eval, n));
+    const size_t nq = (size_t)n_probs * cols, nsq = (size_t)n_probs * scols;
+    if (b.grid_job_dt.grow(nj, kFloor) || b.grid_job_patient.grow(nj, kFloor) ||
+        b.grid_interval_job.grow(interval_job.size(), kFloor) || b.grid_slot_job.grow(cols, kFloor) ||
+        b.grid_offset.grow(P + 1, kFloor) || b.grid_times.grow(cols, kFloor) || b.grid_conc.grow(n * cols, kFloor) ||
+        b.grid_cq.grow(nq, kFloor) || b.grid_cmean.grow(cols, kFloor) || b.grid_ccount.grow(cols, kFloor) ||
+        (want_states && (b.grid_state.grow(n * scols, kFloor) || b.grid_sq.grow(nsq, kFloor) ||
+                         b.grid_smean.grow(scols, kFloor) || b.grid_scount.grow(scols, kFloor))))
+        return BCM3HIP_ERR_ALLOC;
+    for (hipEvent_t& e : b.grid_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    const size_t chunks = (n + nc - 1) / nc;
+    while (b.grid_chunk_ev.size() < 3 * chunks) {
+        hipEvent_t ev;
+        HIPCHK(hipEventCreate(&ev));
+        b.grid_chunk_ev.push_back(ev);
+    }
+    b.grid_timed = false;
+    hipStream_t s = c->stream;
+    HIPCHK(hipEventRecord(b.grid_ev[0], s));
+    int r = stage_batch(c, n, d, values);
+    if (r == 0) r = launch(c, n, c->values, c->logp, c->status, nullptr, nullptr, s);
+    if (r) return r;
+    // (the exponentials' scratch is the launch's: grown only after its kernels were enqueued, and a
+    // DevBuf frees through hipFree, which waits for them)
+    if (b.exps.grow(std::max<size_t>(nc * per_eval, 1), kFloor)) return BCM3HIP_ERR_ALLOC;
+    auto up = [&](void* dst, const void* src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    HIPCHK(up(b.grid_job_dt, job_dt.data(), nj * sizeof(double)));
+    HIPCHK(up(b.grid_job_patient, job_patient.data(), nj * sizeof(int32_t)));
+    HIPCHK(up(b.grid_interval_job, interval_job.data(), interval_job.size() * sizeof(int32_t)));
+    HIPCHK(up(b.grid_slot_job, slot_job.data(), cols * sizeof(int32_t)));
+    HIPCHK(up(b.grid_offset, goff.data(), (P + 1) * sizeof(int32_t)));
+    HIPCHK(up(b.grid_times, gt.data(), cols * sizeof(double)));
+    // the host vectors must outlive the copies (pageable memory: the copy may be staged later)
+    HIPCHK(hipStreamSynchronize(s));
+    ExpmPKDevModel gm = b.m;  // the device model with its job and slot fields swapped, no observation data
+    gm.n_jobs = (int32_t)nj;
+    gm.job_dt = b.grid_job_dt;
+    gm.job_patient = b.grid_job_patient;
+    gm.interval_job = b.grid_interval_job;
+    gm.obs_job = b.grid_slot_job;
+    gm.obs_offset = b.grid_offset;
+    gm.obs_times = b.grid_times;
+    gm.obs_conc = nullptr;
+    gm.n_obs = (int32_t)cols;
+    hipError_t e = hipSuccess;
+    b.grid_chunks = 0;
+    for (size_t i0 = 0; i0 < n && e == hipSuccess; i0 += nc) {
+        const size_t m = std::min(nc, n - i0);
+        hipEvent_t* ev = &b.grid_chunk_ev[3 * b.grid_chunks];
+        HIPCHK(hipEventRecord(ev[0], s));
+        e = launch_expm_pk_exps(gm, (int64_t)m, c->values + i0 * (size_t)c->d, b.exps, s);
+        HIPCHK(hipEventRecord(ev[1], s));
+        if (e == hipSuccess)
+            e = launch_expm_pk_predict(gm, (int64_t)m, (int64_t)i0, c->values, b.exps, 0, b.grid_conc,
+                                       want_states ? b.grid_state.data() : nullptr, nullptr, nullptr, nullptr, s);
+        HIPCHK(hipEventRecord(ev[2], s));
+        b.grid_chunks++;
+    }
+    HIPCHK(hipEventRecord(b.grid_ev[2], s));
+    if (e == hipSuccess)
+        e = launch_predict_quantiles((int64_t)n, (int64_t)cols, b.grid_conc, n_probs, pr, b.grid_cq, b.grid_cmean,
+                                     b.grid_ccount, s);
+    if (e == hipSuccess && want_states)
+        e = launch_predict_quantiles((int64_t)n, (int64_t)scols, b.grid_state, n_probs, pr, b.grid_sq, b.grid_smean,
+                                     b.grid_scount, s);
+    HIPCHK(hipEventRecord(b.grid_ev[3], s));
+    if (e != hipSuccess) {
+        fprintf(stderr, "bcm3hip: time-grid kernel launch failed: %s\n", hipGetErrorString(e));
+        return BCM3HIP_ERR_HIP;
+    }
+    HIPCHK(hipEventRecord(c->scratch_ev, s));  // the exponentials' scratch was used once more
+    auto back = [&](void* dst, const void* src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    HIPCHK(back(logp, c->logp, n * sizeof(double)));
+    HIPCHK(back(status, c->status, n * sizeof(int32_t)));
+    HIPCHK(back(conc_q, b.grid_cq, nq * sizeof(double)));
+    HIPCHK(back(conc_mean, b.grid_cmean, cols * sizeof(double)));
+    HIPCHK(back(conc_count, b.grid_ccount, cols * sizeof(int32_t)));
+    HIPCHK(back(conc_draws, b.grid_conc, n * cols * sizeof(double)));
+    if (want_states) {
+        HIPCHK(back(state_q, b.grid_sq, nsq * sizeof(double)));
+        HIPCHK(back(state_mean, b.grid_smean, scols * sizeof(double)));
+        HIPCHK(back(state_count, b.grid_scount, scols * sizeof(int32_t)));
+        HIPCHK(back(state_draws, b.grid_state, n * scols * sizeof(double)));
+    }
+    HIPCHK(hipEventRecord(b.grid_ev[1], s));
+    HIPCHK(hipStreamSynchronize(s));
+    b.grid_timed = true;
+    return 0;
+}
+
+int bcm3hip_expm_predict_grid_last_ms(bcm3hip_ctx* c, float* exp_ms, float* kernel_ms, float* quantile_ms, float* total_ms)
+{
+    if (!c || c->kind != Kind::ExpmPK || !c->expm.grid_timed) return BCM3HIP_ERR_ARG;
+    auto& b = c->expm;
+    float xs = 0.0f, ks = 0.0f;
+    for (size_t k = 0; k < b.grid_chunks; k++) {
+        float a = 0.0f, p = 0.0f;
+        HIPCHK(hipEventElapsedTime(&a, b.grid_chunk_ev[3 * k], b.grid_chunk_ev[3 * k + 1]));
+        HIPCHK(hipEventElapsedTime(&p, b.grid_chunk_ev[3 * k + 1], b.grid_chunk_ev[3 * k + 2]));
+        xs += a;
+        ks += p;
+    }
+    if (exp_ms) *exp_ms = xs;
+    if (kernel_ms) *kernel_ms = ks;
+    if (quantile_ms) HIPCHK(hipEventElapsedTime(quantile_ms, b.grid_ev[2], b.grid_ev[3]));
+    if (total_ms) HIPCHK(hipEventElapsedTime(total_ms, b.grid_ev[0], b.grid_ev[1]));
     return 0;
 }
 

@@ -26,6 +26,7 @@
 
 #include "pk_math.h"
 #include "popk_kernel.h"
+#include "predict_obs.h"  // predict_t4: the noise stream of the predictive checks
 
 const xm::GlibcPow* bcm3_pow_tables(int* from_libm);  // libm_tables.cpp
 
@@ -458,6 +459,120 @@ __global__ void __launch_bounds__(64) expm_pk_chain_kernel(ExpmPKDevModel m, int
     }
 }
 
+// Predictive checks: one wavefront per (evaluation, patient) walks the same solve on the same
+// exponentials as expm_pk_chain_kernel -- the same products, the same fma order for c and ynew, the
+// same failure rule -- and keeps what that kernel folds away: per output slot col = obs_offset[pj] +
+// oti the observed quantity conc = conv * c, the whole state of the slot (lanes k < n, n contiguous;
+// `state` may be null) and, with observation data (pll, ypred, scales not null), the very term the
+// chain kernel adds and a noise draw of the error model on top of conc. Slots the walk never reaches
+// are written NaN. Everything but the stores is computed by all lanes alike (uniform control flow:
+// the noise draw's rejection loop runs the same way in every lane); the walk's LDS is the state vector,
+// the four scalars and the fail flag (A is there only because construct_matrix fills one; nothing
+// reads it afterwards). Evaluation e of this launch is row row0 + e of values and of the
+// outputs (and of the noise stream); exps holds this launch's evaluations alone.
+__global__ void __launch_bounds__(64) expm_pk_predict_kernel(ExpmPKDevModel m, int64_t nev, int64_t row0,
+                                                             const double* __restrict__ values,
+                                                             const double* __restrict__ exps, uint64_t seed,
+                                                             double* __restrict__ conc, double* __restrict__ state,
+                                                             double* __restrict__ pll, double* __restrict__ ypred,
+                                                             double* __restrict__ scales)
+{
+    __shared__ Mat A;
+    __shared__ double y[NM];
+    __shared__ double scal[4];
+    __shared__ int fail;
+    const int64_t b = blockIdx.x;
+    const int64_t e = b / m.P;
+    const int pj = (int)(b - e * m.P);
+    if (e >= nev) return;
+    const int64_t row = row0 + e;
+    const int j = threadIdx.x;
+    const int n = m.n;
+    const int nn = n * n;
+    const double* v = values + row * m.d;
+    const double* ex = exps + e * (int64_t)m.n_jobs * nn;
+    if (j == 0) {
+        construct_matrix(m, v, pj, A, scal[0], scal[1], scal[2], scal[3]);  // the scalars straight into LDS
+        fail = 0;
+    }
+    if (j < n) y[j] = 0.0;
+    wsync();
+    const double conv = scal[0], add_sd = scal[1], prop_sd = scal[2], bioavailability = scal[3];
+    if (scales && pj == 0 && j == 0) {
+        scales[2 * row] = add_sd;
+        scales[2 * row + 1] = prop_sd;
+    }
+    const int t0 = m.treat_offset[pj], n_treat = m.treat_offset[pj + 1] - t0;
+    const int o0 = m.obs_offset[pj], n_obs = m.obs_offset[pj + 1] - o0;
+    const double* treat_times = m.treat_times + t0;
+    const double* treat_doses = m.treat_doses + t0;
+    const double* obs_times = m.obs_times + o0;
+    const double simulate_until = obs_times[n_obs - 1];
+    const double nan = __builtin_nan("");
+    const int64_t out0 = row * (int64_t)m.n_obs + o0;  // this patient's first column of this row
+    int tti = 0, oti = 0;
+    double current_t = 0.0;
+    while (tti < n_treat && current_t < simulate_until) {
+        const double target_t = (tti < n_treat - 1) ? treat_times[tti + 1] : simulate_until;
+        if (j == 0) y[0] += treat_doses[tti] * bioavailability;
+        wsync();
+        while (oti < n_obs && obs_times[oti] <= target_t) {
+            const double* Eo = ex + (int64_t)m.obs_job[o0 + oti] * nn;  // [col][row]
+            double c = Eo[1] * y[0];
+            for (int k = 1; k < n; k++) c = __builtin_fma(Eo[k * n + 1], y[k], c);
+            const double x = conv * c;
+            const int64_t col = out0 + oti;
+            if (state && j < n) {
+                double s = Eo[j] * y[0];
+                for (int k = 1; k < n; k++) s = __builtin_fma(Eo[k * n + j], y[k], s);
+                state[col * n + j] = s;
+            }
+            if (pll) {
+                double ll = nan, yp = nan;
+                if (!(isnan(x) || isinf(x))) {
+                    const double scale = add_sd + prop_sd * fmax(x, 0.0);
+                    const double yobs = m.obs_conc[o0 + oti];
+                    if (!isnan(yobs)) ll = log_pdf_tnu4(x, yobs, scale);
+                    yp = x + scale * predict_t4(seed, (uint64_t)row, (uint64_t)pj, (uint64_t)oti);
+                }
+                if (j == 0) {
+                    pll[col] = ll;
+                    ypred[col] = yp;
+                }
+            }
+            if (j == 0) conc[col] = x;
+            oti++;
+        }
+        const double* E = ex + (int64_t)m.interval_job[t0 + tti] * nn;
+        double ynew = 0.0;
+        if (j < n) {
+            ynew = E[j] * y[0];
+            for (int k = 1; k < n; k++) ynew = __builtin_fma(E[k * n + j], y[k], ynew);
+        }
+        wsync();
+        if (j < n) {
+            y[j] = ynew;
+            if (isnan(ynew)) fail = 1;
+        }
+        wsync();
+        if (fail) break;
+        current_t = target_t;
+        tti++;
+    }
+    // the slots the walk did not reach
+    for (; oti < n_obs; oti++) {
+        const int64_t col = out0 + oti;
+        if (state && j < n) state[col * n + j] = nan;
+        if (j == 0) {
+            conc[col] = nan;
+            if (pll) {
+                pll[col] = nan;
+                ypred[col] = nan;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // this translation unit's copy of the libm tables (libm_exact.h xm_tables: glibc's exp in the
@@ -490,6 +605,27 @@ hipError_t launch_expm_pk(const ExpmPKDevModel& m, int64_t n, const double* valu
     const hipError_t e = hipGetLastError();
     if (ev_stop) hipEventRecord(ev_stop, stream);
     return e;
+}
+
+hipError_t launch_expm_pk_exps(const ExpmPKDevModel& m, int64_t n, const double* values, double* exps, hipStream_t stream)
+{
+    if (n <= 0 || m.n_jobs <= 0) return hipSuccess;
+    if (n * m.n_jobs > 0x7fffffff) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(expm_pk_exp_kernel, dim3((unsigned)(n * m.n_jobs)), dim3(64), 0, stream, m, n, values, exps,
+                       (const int32_t*)nullptr, (int64_t)0);
+    return hipGetLastError();
+}
+
+hipError_t launch_expm_pk_predict(const ExpmPKDevModel& m, int64_t n, int64_t row0, const double* values,
+                                  const double* exps, uint64_t seed, double* conc, double* state, double* pll,
+                                  double* ypred, double* scales, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    if (!conc || m.P < 1 || n * m.P > 0x7fffffff) return hipErrorInvalidValue;
+    if (pll && (!ypred || !m.obs_conc)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(expm_pk_predict_kernel, dim3((unsigned)(n * m.P)), dim3(64), 0, stream, m, n, row0, values, exps,
+                       seed, conc, state, pll, ypred, scales);
+    return hipGetLastError();
 }
 
 }  // namespace bcm3hip

@@ -124,6 +124,7 @@ std::shared_ptr<Likelihood> LikelihoodFactory::CreateLikelihood(const std::strin
                  type.c_str());
         return ll;
     }
+    ll->SetTypeName(type);
     if (!ll->Initialize(varset, *node, opts)) ll.reset();
     return ll;
 }

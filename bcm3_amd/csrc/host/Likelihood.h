@@ -60,6 +60,10 @@ public:
     //! Backend tuning option (bcm3hip_set_option); false if unsupported.
     virtual bool SetBackendOption(int option, int64_t value) { return false; }
 
+    //! The type="..." of <bcm_likelihood> the factory created this object for (empty otherwise).
+    const std::string& GetTypeName() const { return type_name; }
+    void SetTypeName(const std::string& name) { type_name = name; }
+
     size_t GetNumVariables() const { return varset ? varset->GetNumVariables() : 0; }
     const VariableSet* GetVariableSet() const { return varset.get(); }
 
@@ -68,6 +72,7 @@ protected:
 
     Real learning_rate;
     std::shared_ptr<const VariableSet> varset;
+    std::string type_name;
 };
 
 class LikelihoodFactory {

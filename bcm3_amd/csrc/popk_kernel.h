@@ -80,5 +80,12 @@ hipError_t expm_prepare_device();  // expm_pk_kernel.hip: its copy of the libm t
 hipError_t launch_expm_pk(const ExpmPKDevModel& m, int64_t n, const double* values, double* logp, int32_t* status,
                           double* exps, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop,
                           const int32_t* n_dev = nullptr, int64_t item_base = 0);
+// phase 1 alone: exps[n][n_jobs][n*n] of values[n][d]
+hipError_t launch_expm_pk_exps(const ExpmPKDevModel& m, int64_t n, const double* values, double* exps, hipStream_t stream);
+// expm_pk_predict_kernel on exps[n][...]: evaluation e is row row0 + e of values and of conc [..][n_obs],
+// state [..][n_obs][n] (may be null), pll / ypred [..][n_obs] and scales [..][2] (null without observation data)
+hipError_t launch_expm_pk_predict(const ExpmPKDevModel& m, int64_t n, int64_t row0, const double* values,
+                                  const double* exps, uint64_t seed, double* conc, double* state, double* pll,
+                                  double* ypred, double* scales, hipStream_t stream);
 
 }  // namespace bcm3hip

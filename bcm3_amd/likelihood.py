@@ -37,6 +37,10 @@ def lib() -> C.CDLL:
     L.bcm3_likelihood_predict_status.argtypes = [vp, sz, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.bcm3_likelihood_predict_obs.argtypes = [vp, sz, vp, C.c_uint64, C.c_int, vp] + [vp] * 17
     L.bcm3_likelihood_predict_obs_loo.argtypes = [vp] * 6 + [C.POINTER(C.c_float)]
+    L.bcm3_likelihood_expm_predict_obs.argtypes = [vp, sz, vp, C.c_uint64, C.c_int, vp] + [vp] * 17
+    L.bcm3_likelihood_expm_predict_obs_loo.argtypes = [vp] * 6 + [C.POINTER(C.c_float)]
+    L.bcm3_likelihood_expm_predict_grid.argtypes = [vp, sz, vp, C.c_int, vp, C.c_int, C.c_int, vp] + [vp] * 8
+    L.bcm3_likelihood_expm_predict_last_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.bcm3_likelihood_ccm_track.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int32)]
     L.bcm3_likelihood_ccm_track.restype = C.c_int64
     L.bcm3_table_read.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_int64), vp, C.c_int64]
@@ -232,6 +236,80 @@ class Likelihood:
         if getattr(self, "_loo_ms", None) is None:
             raise RuntimeError("predict_obs_loo_last_ms: no predict_obs_loo has run on this likelihood")
         return self._loo_ms
+
+    @property
+    def is_expm_pk(self) -> bool:
+        """pharmaco_single / pharmaco_population: the family bcm3_amd.predict serves through expm_predict_*"""
+        if getattr(self, "_expm_slots", None) is None:
+            m = _hip.ExpmPKModel()
+            self._expm_slots = _hip.expm_slots(m) if lib().bcm3_likelihood_expm_pk_model(self.h, C.byref(m)) == 0 else False
+        return self._expm_slots is not False
+
+    def expm_slots(self) -> dict:
+        """pharmaco_single / pharmaco_population: P, N, n_obs and the slot metadata patient (int32), time,
+        observed [n_obs] of expm_pk_model()"""
+        if not self.is_expm_pk:
+            self.expm_pk_model()  # raises with the library's message
+        return self._expm_slots
+
+    def expm_predict_obs(self, values, probs, seed: int = 0, pointwise: bool = False) -> dict:
+        """pharmaco_single / pharmaco_population: predicted measurements of values [n, d] on the flat
+        observation axis (bcm3_likelihood_expm_predict_obs; bcm3_amd.predict.measurements is the front end),
+        the arrays of _hip.Context.expm_predict_obs plus patient, time, observed [n_obs]."""
+        s = self._expm_slots if self.is_expm_pk else dict(n_obs=0)  # the library refuses other types itself
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        out = _hip.expm_predict_obs_outputs(n, p.size, s["n_obs"], pointwise)
+        r = lib().bcm3_likelihood_expm_predict_obs(self.h, n, v.ctypes.data, int(seed) & (2**64 - 1), p.size,
+                                                   p.ctypes.data, *_hip.predict_obs_pointers(out))
+        if r != 0:
+            _err("bcm3_likelihood_expm_predict_obs", r)
+        out = {k: a for k, a in out.items() if a is not None}
+        out.update(patient=s["patient"], time=s["time"], observed=s["observed"])
+        return out
+
+    def expm_predict_obs_loo(self) -> dict:
+        """the PSIS-LOO terms [n_obs] of the last expm_predict_obs (bcm3_likelihood_expm_predict_obs_loo)"""
+        cols = self._expm_slots["n_obs"] if self.is_expm_pk else 0
+        out = {k: np.empty(cols, dtype=np.int32 if k in _hip.PSIS_INT_KEYS else np.float64) for k in _hip.PSIS_KEYS}
+        ms = C.c_float()
+        r = lib().bcm3_likelihood_expm_predict_obs_loo(self.h, *(out[k].ctypes.data for k in _hip.PSIS_KEYS),
+                                                       C.byref(ms))
+        if r != 0:
+            _err("bcm3_likelihood_expm_predict_obs_loo", r)
+        self._loo_ms = float(ms.value)
+        return out
+
+    def expm_predict_grid(self, values, probs, times, states: bool = False) -> dict:
+        """pharmaco_single / pharmaco_population: every patient simulated at times [G]
+        (bcm3_likelihood_expm_predict_grid; bcm3_amd.predict.posterior_predictive is the front end), the
+        arrays of _hip.Context.expm_predict_grid."""
+        s = self._expm_slots if self.is_expm_pk else dict(P=0, N=0)
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        out = _hip.expm_predict_grid_outputs(n, p.size, s["P"], t.size, s["N"], states)
+        ptrs = _hip.predict_obs_pointers(out)[:8]
+        r = lib().bcm3_likelihood_expm_predict_grid(self.h, n, v.ctypes.data, t.size, t.ctypes.data, int(bool(states)),
+                                                    p.size, p.ctypes.data, *ptrs)
+        if r != 0:
+            _err("bcm3_likelihood_expm_predict_grid", r)
+        out = {k: a for k, a in out.items() if a is not None}
+        out["time"] = t
+        return out
+
+    def expm_predict_last_ms(self, which: str = "obs"):
+        """HIP-event ms of the last expm_predict_obs ("obs": predict kernel, quantile launches, WAIC kernel,
+        whole call) or expm_predict_grid ("grid": the grid's exponentials, predict kernel, quantile launches,
+        whole call)"""
+        ms = (C.c_float * 4)()
+        args = (ms, None) if which == "obs" else (None, ms)
+        r = lib().bcm3_likelihood_expm_predict_last_ms(self.h, *args)
+        if r != 0:
+            _err("bcm3_likelihood_expm_predict_last_ms", r)
+        return tuple(float(x) for x in ms)
 
     def ccm_track(self):
         """cell_cycle_marker: (track index, the track's frames [T]) the likelihood evaluates against

@@ -3,7 +3,10 @@ to quantiles, mean and count per patient, state and time point (DESIGN.md §4 "p
 
 The solve writes the trajectories of all draws into device memory, the quantile kernel
 (bcm3_amd/csrc/predict_kernels.hip) sorts every column there, and only the bands come back to the
-host. For pop_pk_trajectory and pharmacokinetic_trajectory likelihoods.
+host. For pop_pk_trajectory and pharmacokinetic_trajectory likelihoods, and for pharmaco_single and
+pharmaco_population (the matrix-exponential PK kernels; objects with a true `is_expm_pk`), whose
+observations lie on a flat axis [n_obs] with `patient` [n_obs] naming each one's patient and whose bands
+are drawn on a time grid (DESIGN.md §4 "predictive checks of the matrix-exponential PK family").
 """
 from __future__ import annotations
 
@@ -37,7 +40,25 @@ def _check(ll, samples, probs, what):
     return v, p
 
 
-def posterior_predictive(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95)) -> dict:
+def _is_expm(ll) -> bool:
+    """a pharmaco_single / pharmaco_population Likelihood or a matrix-exponential PK Context"""
+    return bool(getattr(ll, "is_expm_pk", False))
+
+
+def _expm_posterior_predictive(ll, v, p, times, states) -> dict:
+    s = ll.expm_slots()
+    if times is None:
+        times = np.linspace(0.0, float(np.max(s["time"])), 101)
+    t = _hip.expm_grid_check(v.shape[0], s["P"], s["N"], times)  # before any device call
+    raw = ll.expm_predict_grid(v, p, t, states=states)
+    out = dict(concentration=dict(quantiles=raw["conc_q"], mean=raw["conc_mean"], count=raw["conc_count"]),
+               time=t, logp=raw["logp"], status=raw["status"])
+    if states:
+        out["states"] = dict(quantiles=raw["state_q"], mean=raw["state_mean"], count=raw["state_count"])
+    return out
+
+
+def posterior_predictive(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95), times=None, states: bool = False) -> dict:
     """The bands of samples [n, d] (parameter vectors in the likelihood's variable order) under a
     bcm3_amd.likelihood.Likelihood or a PopPK bcm3_amd._hip.Context:
 
@@ -48,9 +69,23 @@ def posterior_predictive(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95)
       logp, status [n]                 as evaluate_batch returns them
       time [T]                         the output times
 
+    Under a pharmaco_single / pharmaco_population likelihood (or a matrix-exponential PK Context) every
+    patient is simulated at `times` [G] (None: 101 equally spaced points from 0 to the largest observation
+    time of any patient; at most 1024, finite, >= 0, non-decreasing, the last one > 0):
+
+      concentration  dict(quantiles [len(probs), P, G], mean, count [P, G]) of the quantity the likelihood
+                     observes
+      states         with states=True, dict(quantiles [len(probs), P, G, N], mean, count [P, G, N]) of every
+                     compartment
+      time [G], logp, status [n]
+
     At most MAX_SAMPLES (8192) samples per call: more raises ValueError -- thin the draws first."""
     ll = likelihood_or_context
     v, p = _check(ll, samples, probs, "posterior_predictive")
+    if _is_expm(ll):
+        return _expm_posterior_predictive(ll, v, p, times, states)
+    if times is not None or states:
+        raise ValueError("times and states apply to pharmaco_single / pharmaco_population likelihoods only")
     out = ll.predict(v, p)
     if "time" not in out:
         out["time"] = np.array(ll.time, dtype=np.float64)
@@ -128,13 +163,26 @@ def select_run(path: str, burn_in=None, thin: int = 1) -> dict:
 
 
 def from_output(path: str, likelihood, temperature_index: int = -1, burn_in: int = 0, thin: int = 1,
-                probs=(0.05, 0.5, 0.95)) -> dict:
+                probs=(0.05, 0.5, 0.95), times=None, states: bool = False) -> dict:
     """posterior_predictive on the samples of an output.nc: temperature temperature_index (-1: the
     last, the posterior at T = 1), the first burn_in samples dropped, every thin-th of the rest kept.
     The file's variable names must be the likelihood's, in order; a mismatch is an error that names
-    the variable."""
+    the variable. times and states: the time grid of a pharmaco_single / pharmaco_population likelihood."""
     rows = select_samples(path, getattr(likelihood, "variable_names", None), temperature_index, burn_in, thin)
-    return posterior_predictive(likelihood, rows, probs)
+    if times is None and not states:
+        return posterior_predictive(likelihood, rows, probs)
+    return posterior_predictive(likelihood, rows, probs, times, states)
+
+
+def coverage_by_patient(observed, lower, upper, patient, P: int) -> np.ndarray:
+    """coverage on a flat observation axis: observed, lower, upper, patient [n_obs] -> [P]"""
+    obs = np.asarray(observed, dtype=np.float64)
+    have = ~np.isnan(obs) & ~np.isnan(lower) & ~np.isnan(upper)
+    with np.errstate(invalid="ignore"):
+        inside = have & (obs >= lower) & (obs <= upper)
+    cnt = np.bincount(np.asarray(patient)[have], minlength=P)
+    ins = np.bincount(np.asarray(patient)[inside], minlength=P)
+    return np.where(cnt > 0, ins / np.maximum(cnt, 1), np.nan)
 
 
 def coverage(observed, lower, upper) -> np.ndarray:
@@ -219,23 +267,35 @@ def measurements(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95), seed: 
                      n_high_k of which have pareto_k > k_threshold: there the estimate is not to be
                      trusted, and the model fits that measurement badly
 
+    Under a pharmaco_single / pharmaco_population likelihood the [P, T] axes are one flat axis [n_obs], the
+    patients' own observations concatenated in patient order: observed, time and patient [n_obs] say
+    what, when and whose each column is, and coverage [P] is grouped by patient.
+
     At most MAX_SAMPLES (8192) samples per call: more raises ValueError -- thin the draws first."""
     ll = likelihood_or_context
     v, p = _check(ll, samples, probs, "measurements")
-    raw = ll.predict_obs(v, p, seed=seed, pointwise=pointwise)
+    expm = _is_expm(ll)
+    raw = ll.expm_predict_obs(v, p, seed=seed, pointwise=pointwise) if expm else ll.predict_obs(v, p, seed=seed,
+                                                                                                 pointwise=pointwise)
     observed = raw["observed"] if "observed" in raw else np.array(ll.observed, dtype=np.float64)
     out = dict(concentration=dict(quantiles=raw["conc_q"], mean=raw["conc_mean"], count=raw["conc_count"]),
                predicted=dict(quantiles=raw["pred_q"], mean=raw["pred_mean"], count=raw["pred_count"]),
                observed=observed, time=raw["time"] if "time" in raw else np.array(ll.time, dtype=np.float64),
                logp=raw["logp"], status=raw["status"])
     order = np.argsort(p, kind="stable")
-    out["coverage"] = coverage(observed, raw["pred_q"][order[0]], raw["pred_q"][order[-1]])
+    if expm:  # the flat observation axis [n_obs], grouped by patient
+        s = ll.expm_slots()
+        out["patient"] = np.array(s["patient"], dtype=np.int32)
+        out["coverage"] = coverage_by_patient(observed, raw["pred_q"][order[0]], raw["pred_q"][order[-1]], out["patient"],
+                                              s["P"])
+    else:
+        out["coverage"] = coverage(observed, raw["pred_q"][order[0]], raw["pred_q"][order[-1]])
     tot = waic_totals(raw["waic_count"], raw["lppd"], raw["p_waic"], raw["elpd"])
     out["waic"] = dict(count=raw["waic_count"], lppd=raw["lppd"], mean=raw["llh_mean"], p_waic=raw["p_waic"],
                        elpd=raw["elpd"], elpd_waic=tot["elpd_waic"], p_waic_total=tot["p_waic"],
                        lppd_total=tot["lppd"], se=tot["se"], n_obs=tot["n_obs"])
     if loo:  # on the pointwise log-likelihoods predict_obs left on the device
-        t = ll.predict_obs_loo()
+        t = ll.expm_predict_obs_loo() if expm else ll.predict_obs_loo()
         with np.errstate(invalid="ignore"):
             p_loo = raw["lppd"] - t["elpd_loo"]
         tot = loo_totals(t["count"], t["elpd_loo"], raw["lppd"], t["pareto_k"], k_threshold)

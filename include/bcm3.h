@@ -78,6 +78,28 @@ int bcm3_likelihood_predict_obs(bcm3_likelihood* ll, size_t n, const double* val
  * the kernel's HIP-event time (may be NULL). -3 when no such result is current. */
 int bcm3_likelihood_predict_obs_loo(bcm3_likelihood* ll, int32_t* count, int32_t* tail, double* pareto_k,
                                     double* elpd_loo, double* n_eff, float* loo_ms);
+/* The same checks for pharmaco_single and pharmaco_population (bcm3hip_expm_predict_obs /
+ * _predict_obs_loo / _predict_grid on the likelihood's context; see bcm3hip.h for every array). The
+ * observation axis is flat: n_obs columns in the concatenated patient-major order of
+ * bcm3_likelihood_expm_pk_model. The grid call simulates every patient at times[G] and reduces the
+ * concentration to conc_q[n_probs][P][G] and, with want_states, every compartment to
+ * state_q[n_probs][P][G][N]. -2 for another likelihood type (the message names it) or a likelihood
+ * without a device, -3 when the device call fails. */
+int bcm3_likelihood_expm_predict_obs(bcm3_likelihood* ll, size_t n, const double* values, uint64_t seed, int n_probs,
+                                     const double* probs, double* conc_q, double* conc_mean, int32_t* conc_count,
+                                     double* pred_q, double* pred_mean, int32_t* pred_count, int32_t* waic_count,
+                                     double* lppd, double* llh_mean, double* p_waic, double* elpd, double* logp,
+                                     int32_t* status, double* conc, double* ypred, double* pll, double* scales);
+int bcm3_likelihood_expm_predict_obs_loo(bcm3_likelihood* ll, int32_t* count, int32_t* tail, double* pareto_k,
+                                         double* elpd_loo, double* n_eff, float* loo_ms);
+int bcm3_likelihood_expm_predict_grid(bcm3_likelihood* ll, size_t n, const double* values, int G, const double* times,
+                                      int want_states, int n_probs, const double* probs, double* conc_q,
+                                      double* conc_mean, int32_t* conc_count, double* state_q, double* state_mean,
+                                      int32_t* state_count, double* logp, int32_t* status);
+/* HIP-event times in ms of the likelihood's last expm_predict_obs (obs_ms[4]: predict kernel, quantile
+ * launches, WAIC kernel, whole call) and last expm_predict_grid (grid_ms[4]: the grid's exponentials,
+ * predict kernel, quantile launches, whole call); either may be NULL; -3 when that call has not run. */
+int bcm3_likelihood_expm_predict_last_ms(bcm3_likelihood* ll, float* obs_ms, float* grid_ms);
 /* cell_cycle_marker: the track the likelihood evaluates against (the row ccm.track_ix selected):
  * copies up to cap frames into data (may be NULL) and the row index into *track_ix (may be NULL);
  * returns the number of frames, -2 for other likelihood types. */

@@ -426,9 +426,13 @@ enum {
                                        sharing a SIMD */
     BCM3HIP_OPT_PLACEMENT_LOG = 6,  /* diagnostics, PopPK one-trajectory-per-wavefront launches: 1 = each
                                        trajectory records where and when it ran (see placement_log) */
-    BCM3HIP_OPT_CCM_ONE_LANE = 7    /* tests and measurements, cell_cycle_marker contexts: 1 = the
+    BCM3HIP_OPT_CCM_ONE_LANE = 7,   /* tests and measurements, cell_cycle_marker contexts: 1 = the
                                        one-lane-per-evaluation kernel instead of one wavefront per
                                        evaluation (default 0); same results */
+    BCM3HIP_OPT_EXPM_SCRATCH_BYTES = 8 /* tests and measurements, matrix-exponential PK contexts: the
+                                       byte cap of the exponentials' scratch, which sets how many
+                                       evaluations one chunk of a launch takes; 0 = the default of
+                                       1 GiB; same results */
 };
 
 int bcm3hip_device_count(void);
@@ -1058,6 +1062,66 @@ int bcm3hip_predict_obs_loo(bcm3hip_ctx* ctx, int32_t* count, int32_t* tail, dou
                             double* n_eff);
 /* HIP-event time of the kernel of the context's last bcm3hip_predict_obs_loo. */
 int bcm3hip_predict_obs_loo_last_ms(bcm3hip_ctx* ctx, float* loo_ms);
+
+/* ---- Predictive checks of the matrix-exponential PK likelihoods (expm_pk_kernel.hip) ----
+ * pharmaco_single / pharmaco_population contexts (bcm3hip_open_expm_pk); every other kind is
+ * BCM3HIP_ERR_ARG before any launch. The observation axis is flat: n_obs columns, the model's
+ * concatenated patient-major order (column obs_offset[j] + i is observation i of patient j). */
+#define BCM3HIP_EXPM_GRID_MAX 1024
+#define BCM3HIP_EXPM_PREDICT_MAX_BYTES ((uint64_t)4 << 30)
+/* The step lengths PharmacokineticModel::Solve (.cpp:127-174) exponentiates when patient j's doses
+ * are treat_times[treat_offset[j], treat_offset[j+1]) and its output slots slot_times[slot_offset[j],
+ * slot_offset[j+1]) (ascending; the solve runs until the patient's last slot): job_dt / job_patient
+ * [*n_jobs] (room for n_treat + n_slots each), every value by the loop's own subtraction, equal values
+ * of one patient sharing a job; interval_job[n_treat] the job of the step that ends dose interval i and
+ * slot_job[n_slots] the job of the offset from the interval start to slot i, -1 where the loop never
+ * gets there. Needs no device. BCM3HIP_ERR_ARG for P < 1, a NULL pointer, offsets that do not start
+ * at 0 or decrease, or a patient without a dose or a slot. */
+int bcm3hip_expm_jobs_host(int P, const int32_t* treat_offset, const double* treat_times, const int32_t* slot_offset,
+                           const double* slot_times, int32_t* n_jobs, double* job_dt, int32_t* job_patient,
+                           int32_t* interval_job, int32_t* slot_job);
+/* bcm3hip_predict_obs for these contexts, the [P][T] axes replaced by [n_obs]: the ordinary launch for
+ * logp / status, then one wavefront per (draw e, patient j) walks the solve again on the same
+ * exponentials and leaves, per observation column,
+ *   conc  = conv * c, conv = (1e6 / MW) / vod and c the central compartment: what the likelihood observes
+ *   pll   = LogPdfTnu4(conc, observed, add_sd + prop_sd * max(conc, 0)), the term the launch added to the
+ *           patient's log-likelihood, bit for bit; NaN where conc is not finite or observed is NaN
+ *   ypred = conc + (add_sd + prop_sd * max(conc, 0)) * tau(seed, e, j, i), i the observation's index
+ *           within its patient (bcm3hip_t4_draws_host); NaN where conc is not finite
+ * and scales[e] = (add_sd, prop_sd). Columns a solve never reaches (a NaN state ended it) are NaN.
+ * Reductions, copies and NULL rules as bcm3hip_predict_obs. Draws go through the exponentials in
+ * chunks under the scratch cap (BCM3HIP_OPT_EXPM_SCRATCH_BYTES); the result does not depend on it. */
+int bcm3hip_expm_predict_obs(bcm3hip_ctx* ctx, size_t n, size_t d, const double* values, uint64_t seed, int n_probs,
+                             const double* probs, double* conc_q, double* conc_mean, int32_t* conc_count, double* pred_q,
+                             double* pred_mean, int32_t* pred_count, int32_t* waic_count, double* lppd, double* llh_mean,
+                             double* p_waic, double* elpd, double* logp, int32_t* status, double* conc, double* ypred,
+                             double* pll, double* scales);
+/* HIP-event times of the context's last bcm3hip_expm_predict_obs (any may be NULL): the predict kernel
+ * alone (summed over the chunks of the launch), the two quantile launches, the WAIC kernel, the whole call. */
+int bcm3hip_expm_predict_obs_last_ms(bcm3hip_ctx* ctx, float* kernel_ms, float* quantile_ms, float* waic_ms,
+                                     float* total_ms);
+/* bcm3hip_column_psis_loo over the pll[n][n_obs] the context's last bcm3hip_expm_predict_obs left on the
+ * device; the five arrays [n_obs] (any may be NULL). BCM3HIP_ERR_ARG when no such result is current:
+ * before the first one, and after any later evaluation or predictive call on the context. */
+int bcm3hip_expm_predict_obs_loo(bcm3hip_ctx* ctx, int32_t* count, int32_t* tail, double* pareto_k, double* elpd_loo,
+                                 double* n_eff);
+int bcm3hip_expm_predict_obs_loo_last_ms(bcm3hip_ctx* ctx, float* loo_ms);
+/* Bands on a time grid (the reference's GetSimulatedTrajectory over draws): every patient simulated
+ * at the same times[G] until times[G-1], all compartments kept. times finite, >= 0, non-decreasing,
+ * times[G-1] > 0, 1 <= G <= BCM3HIP_EXPM_GRID_MAX, and n * P * G * (N + 1) * 8 bytes of trajectories
+ * at most BCM3HIP_EXPM_PREDICT_MAX_BYTES; anything else is BCM3HIP_ERR_ARG before any launch.
+ * Copies back conc_q[n_probs][P][G], conc_mean / conc_count [P][G] (may be NULL); with want_states
+ * state_q[n_probs][P][G][N], state_mean / state_count [P][G][N]; logp[n] and status[n] (may be NULL) of
+ * the ordinary launch. conc_draws[n][P][G] and state_draws[n][P][G][N] (tests; NULL otherwise) are the
+ * trajectories themselves. Synchronous. */
+int bcm3hip_expm_predict_grid(bcm3hip_ctx* ctx, size_t n, size_t d, const double* values, int G, const double* times,
+                              int want_states, int n_probs, const double* probs, double* conc_q, double* conc_mean,
+                              int32_t* conc_count, double* state_q, double* state_mean, int32_t* state_count,
+                              double* logp, int32_t* status, double* conc_draws, double* state_draws);
+/* HIP-event times of the context's last bcm3hip_expm_predict_grid (any may be NULL): the grid's
+ * exponentials, the predict kernel, the quantile launches, the whole call. */
+int bcm3hip_expm_predict_grid_last_ms(bcm3hip_ctx* ctx, float* exp_ms, float* kernel_ms, float* quantile_ms,
+                                      float* total_ms);
 
 #ifdef __cplusplus
 }
