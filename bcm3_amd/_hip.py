@@ -426,6 +426,61 @@ def expm_grid_check(n: int, P: int, N: int, times):
     return t
 
 
+# ---- predictive checks of the cell_cycle_marker likelihood (frame axis [T]) ----
+CCM_GRID_MAX = 4096                # BCM3HIP_CCM_GRID_MAX
+CCM_EVENTS = ("S_entry", "plateau", "mitosis")
+
+
+def ccm_predict_host(data, values, seed: int = 0, frames=None) -> dict:
+    """bcm3hip_ccm_predict_host: the cell_cycle_marker predict kernel's source compiled for the host --
+    signal [n, G] (G = frames, None: T), pll, ypred [n, T], scales [n, 2], events [n, 3] of values
+    [n, 10] against the track data [T]. Needs no device."""
+    t = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, CCM_NVARS)
+    n, T = v.shape[0], t.size
+    G = T if frames is None else int(frames)
+    out = dict(signal=np.empty((n, max(G, 0))), pll=np.empty((n, T)), ypred=np.empty((n, T)), scales=np.empty((n, 2)),
+               events=np.empty((n, 3)))
+    m = CcmModel(T, t.ctypes.data)
+    check(lib().bcm3hip_ccm_predict_host(C.byref(m), n, v.ctypes.data, int(seed) & (2**64 - 1), G,
+                                         *(out[k].ctypes.data for k in ("signal", "pll", "ypred", "scales", "events"))),
+          "bcm3hip_ccm_predict_host")
+    return out
+
+
+def ccm_predict_obs_outputs(n: int, k: int, T: int, pointwise: bool) -> dict:
+    """the outputs of bcm3hip_ccm_predict_obs in argument order"""
+    i = np.int32
+    out = dict(sig_q=np.empty((k, T)), sig_mean=np.empty(T), sig_count=np.empty(T, dtype=i),
+               pred_q=np.empty((k, T)), pred_mean=np.empty(T), pred_count=np.empty(T, dtype=i),
+               waic_count=np.empty(T, dtype=i), lppd=np.empty(T), llh_mean=np.empty(T),
+               p_waic=np.empty(T), elpd=np.empty(T), logp=np.empty(n), status=np.empty(n, dtype=i))
+    for key in ("signal", "ypred", "pll"):
+        out[key] = np.empty((n, T)) if pointwise else None
+    out["scales"] = np.empty((n, 2)) if pointwise else None
+    return out
+
+
+def ccm_predict_grid_outputs(n: int, k: int, G: int, pointwise: bool, events: bool = True) -> dict:
+    """the outputs of bcm3hip_ccm_predict_grid in argument order (events: with the event draws, which
+    bcm3_likelihood_ccm_predict_grid does not return)"""
+    i = np.int32
+    out = dict(sig_q=np.empty((k, G)), sig_mean=np.empty(G), sig_count=np.empty(G, dtype=i),
+               event_q=np.empty((k, 3)), event_mean=np.empty(3), event_count=np.empty(3, dtype=i),
+               logp=np.empty(n), status=np.empty(n, dtype=i), signal=np.empty((n, G)) if pointwise else None)
+    if events:
+        out["events"] = np.empty((n, 3)) if pointwise else None
+    return out
+
+
+def ccm_frames_check(frames, T: int) -> int:
+    """the frame count G of bcm3hip_ccm_predict_grid (None: the track length T); ValueError outside its limits"""
+    G = int(T) if frames is None else int(frames)
+    if not 1 <= G <= CCM_GRID_MAX:
+        raise ValueError(f"between 1 and {CCM_GRID_MAX} frames per call, got {G}")
+    return G
+
+
 STATS_DTYPE = np.dtype([(k, np.int32) for k in ("nst", "nfe", "nni", "nsetups", "nje", "netf", "ncfn", "nreinit")])
 
 _lib = None
@@ -543,6 +598,17 @@ def lib() -> C.CDLL:
     for f in ("bcm3hip_expm_jobs_host", "bcm3hip_expm_predict_obs", "bcm3hip_expm_predict_obs_last_ms",
               "bcm3hip_expm_predict_obs_loo", "bcm3hip_expm_predict_obs_loo_last_ms", "bcm3hip_expm_predict_grid",
               "bcm3hip_expm_predict_grid_last_ms"):
+        getattr(L, f).restype = C.c_int
+    L.bcm3hip_ccm_predict_host.argtypes = [C.POINTER(CcmModel), i64, vp, C.c_uint64, C.c_int] + [vp] * 5
+    L.bcm3hip_ccm_predict_obs.argtypes = [vp, sz, sz, vp, C.c_uint64, C.c_int, vp] + [vp] * 17
+    L.bcm3hip_ccm_predict_obs_last_ms.argtypes = [vp] + [fp] * 4
+    L.bcm3hip_ccm_predict_obs_loo.argtypes = [vp] * 6
+    L.bcm3hip_ccm_predict_obs_loo_last_ms.argtypes = [vp, fp]
+    L.bcm3hip_ccm_predict_grid.argtypes = [vp, sz, sz, vp, C.c_int, C.c_int, vp] + [vp] * 10
+    L.bcm3hip_ccm_predict_grid_last_ms.argtypes = [vp] + [fp] * 3
+    for f in ("bcm3hip_ccm_predict_host", "bcm3hip_ccm_predict_obs", "bcm3hip_ccm_predict_obs_last_ms",
+              "bcm3hip_ccm_predict_obs_loo", "bcm3hip_ccm_predict_obs_loo_last_ms", "bcm3hip_ccm_predict_grid",
+              "bcm3hip_ccm_predict_grid_last_ms"):
         getattr(L, f).restype = C.c_int
     for f in ("bcm3hip_open_popk", "bcm3hip_open_analytic", "bcm3hip_open_mixture", "bcm3hip_open_expm_pk", "bcm3hip_close", "bcm3hip_set_option",
               "bcm3hip_num_variables", "bcm3hip_eval_batch", "bcm3hip_eval_batch_device",
@@ -692,7 +758,68 @@ class Context:
         m = CcmModel(t.size, t.ctypes.data)
         h = C.c_void_p()
         check(lib().bcm3hip_open_cell_cycle_marker(device, C.byref(m), C.byref(h)), "bcm3hip_open_cell_cycle_marker")
-        return cls(h, CCM_NVARS, T=int(t.size))
+        ctx = cls(h, CCM_NVARS, T=int(t.size))
+        ctx._ccm_track = t.copy()
+        return ctx
+
+    @property
+    def is_ccm(self) -> bool:
+        """a cell_cycle_marker context: the family bcm3_amd.predict serves through ccm_predict_*"""
+        return getattr(self, "_ccm_track", None) is not None
+
+    def ccm_track(self):
+        """cell_cycle_marker contexts: (0, the track's frames [T]), as Likelihood.ccm_track returns them"""
+        if not self.is_ccm:
+            raise RuntimeError("ccm_track: not a cell_cycle_marker context")
+        return 0, self._ccm_track
+
+    def ccm_predict_obs(self, values: np.ndarray, probs, seed: int = 0, pointwise: bool = False) -> dict:
+        """bcm3hip_ccm_predict_obs (cell_cycle_marker contexts): predict_obs on the frame axis -- sig_q, pred_q
+        [n_probs, T], their _mean and _count, the WAIC terms [T], logp, status [n]; with pointwise also signal,
+        ypred, pll [n, T] and scales [n, 2]."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        # (another kind of context has no track: the library refuses it)
+        out = ccm_predict_obs_outputs(n, p.size, self.T if self.is_ccm else 0, pointwise)
+        check(lib().bcm3hip_ccm_predict_obs(self.h, n, self.d, _ptr(v), int(seed) & (2**64 - 1), p.size, _ptr(p),
+                                            *predict_obs_pointers(out)), "bcm3hip_ccm_predict_obs")
+        return {k: a for k, a in out.items() if a is not None}
+
+    def ccm_predict_obs_loo(self) -> dict:
+        """bcm3hip_ccm_predict_obs_loo: the PSIS-LOO terms [T] of the pointwise log-likelihoods the last
+        ccm_predict_obs left on the device. Raises when no such result is current."""
+        cols = self.T if self.is_ccm else 0
+        out = {k: np.empty(cols, dtype=np.int32 if k in PSIS_INT_KEYS else np.float64) for k in PSIS_KEYS}
+        check(lib().bcm3hip_ccm_predict_obs_loo(self.h, *(_ptr(out[k]) for k in PSIS_KEYS)),
+              "bcm3hip_ccm_predict_obs_loo")
+        return out
+
+    def ccm_predict_grid(self, values: np.ndarray, probs, frames=None, pointwise: bool = False) -> dict:
+        """bcm3hip_ccm_predict_grid: the signal on frames 0 .. G-1 (G = frames, None: T) -- sig_q [n_probs, G],
+        sig_mean, sig_count [G] -- and the event times (S entry, plateau, mitosis) -- event_q [n_probs, 3],
+        event_mean, event_count [3]; logp, status [n]. pointwise also returns signal [n, G] and events [n, 3]."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        G = int(self.T if frames is None else frames)
+        out = ccm_predict_grid_outputs(n, p.size, max(G, 0), pointwise)
+        check(lib().bcm3hip_ccm_predict_grid(self.h, n, self.d, _ptr(v), G, p.size, _ptr(p),
+                                             *predict_obs_pointers(out)), "bcm3hip_ccm_predict_grid")
+        out = {k: a for k, a in out.items() if a is not None}
+        out["frame"] = np.arange(G, dtype=np.float64)
+        return out
+
+    def ccm_predict_last_ms(self, which: str = "obs"):
+        """HIP-event ms of the last ccm_predict_obs ("obs": predict kernel, quantile launches, WAIC kernel,
+        whole call), ccm_predict_obs_loo ("loo": the PSIS-LOO kernel) or ccm_predict_grid ("grid": predict
+        kernel, quantile launches, whole call)"""
+        k = {"obs": 4, "loo": 1, "grid": 3}[which]
+        ms = [C.c_float() for _ in range(k)]
+        f = getattr(lib(), {"obs": "bcm3hip_ccm_predict_obs_last_ms", "loo": "bcm3hip_ccm_predict_obs_loo_last_ms",
+                            "grid": "bcm3hip_ccm_predict_grid_last_ms"}[which])
+        check(f(self.h, *(C.byref(x) for x in ms)), f"bcm3hip_ccm_predict_{which}_last_ms")
+        return tuple(float(x.value) for x in ms)
 
     def set_option(self, opt: int, value: int):
         check(lib().bcm3hip_set_option(self.h, opt, int(value)), "bcm3hip_set_option")

@@ -162,6 +162,25 @@ struct bcm3hip_ctx {
     struct {
         CcmDevModel m{};
         bool one_lane = false;  // BCM3HIP_OPT_CCM_ONE_LANE
+        // bcm3hip_ccm_predict_obs: signal, ypred, pll [n][T] and scales [n][2]; the bands of signal and
+        // ypred; the WAIC terms of pll ([4][T]); its events (whole call, then the boundaries of the
+        // predict kernel, the quantile launches, the WAIC kernel); the rows of pll that are the
+        // context's current result (0: none -- every launch of the context resets it)
+        DevBuf<double> obs_signal, obs_ypred, obs_pll, obs_scales, obs_sq, obs_smean, obs_pq, obs_pmean, obs_waic;
+        DevBuf<int32_t> obs_scount, obs_pcount, obs_wcount;
+        hipEvent_t obs_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        bool obs_timed = false;
+        size_t obs_rows = 0;
+        DevBuf<double> loo_terms;
+        DevBuf<int32_t> loo_count, loo_tail;
+        hipEvent_t loo_ev[2] = {nullptr, nullptr};
+        bool loo_timed = false;
+        // bcm3hip_ccm_predict_grid: signal [n][G] and events [n][3], their bands, and its events (whole
+        // call, then the boundaries of the predict kernel and the quantile launches)
+        DevBuf<double> grid_signal, grid_events, grid_sq, grid_smean, grid_eq, grid_emean;
+        DevBuf<int32_t> grid_scount, grid_ecount;
+        hipEvent_t grid_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        bool grid_timed = false;
     } ccm;
 };
 
@@ -758,6 +777,12 @@ int bcm3hip_close(bcm3hip_ctx* c)
         if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->expm.grid_ev)
         if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->ccm.obs_ev)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->ccm.loo_ev)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->ccm.grid_ev)
+        if (e) hipEventDestroy(e);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return 0;
@@ -900,6 +925,7 @@ static int launch(bcm3hip_ctx* c, size_t n, const double* dvalues, double* dlogp
     if ((n_dev || dsteps) && !takes_device_count(c)) return BCM3HIP_ERR_ARG;
     c->popk.obs_rows = 0;  // whatever predict_obs left is no longer the context's last result
     c->expm.obs_rows = 0;
+    c->ccm.obs_rows = 0;
     hipError_t e = hipSuccess;
     if (c->scratch_used && c->scratch_stream != s) HIPCHK(hipStreamWaitEvent(s, c->scratch_ev, 0));
     hipEvent_t e0 = c->ev0, e1 = c->ev1;
@@ -1598,6 +1624,203 @@ int bcm3hip_expm_predict_grid_last_ms(bcm3hip_ctx* c, float* exp_ms, float* kern
     if (exp_ms) *exp_ms = xs;
     if (kernel_ms) *kernel_ms = ks;
     if (quantile_ms) HIPCHK(hipEventElapsedTime(quantile_ms, b.grid_ev[2], b.grid_ev[3]));
+    if (total_ms) HIPCHK(hipEventElapsedTime(total_ms, b.grid_ev[0], b.grid_ev[1]));
+    return 0;
+}
+
+// ---- predictive checks of the cell_cycle_marker contexts ----
+
+int bcm3hip_ccm_predict_obs(bcm3hip_ctx* c, size_t n, size_t d, const double* values, uint64_t seed, int n_probs,
+                            const double* probs, double* sig_q, double* sig_mean, int32_t* sig_count, double* pred_q,
+                            double* pred_mean, int32_t* pred_count, int32_t* waic_count, double* lppd, double* llh_mean,
+                            double* p_waic, double* elpd, double* logp, int32_t* status, double* signal, double* ypred,
+                            double* pll, double* scales)
+{
+    if (!c || c->kind != Kind::Ccm || (int)d != c->d || !values || !sig_q || !pred_q || !logp) return BCM3HIP_ERR_ARG;
+    PredictProbs pr{};
+    if (!predict_args_ok(n, n_probs, probs, pr)) return BCM3HIP_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    auto& b = c->ccm;
+    const size_t cols = (size_t)b.m.T;  // signal, ypred, pll [n][T] as data[n][cols]
+    const size_t nq = (size_t)n_probs * cols;
+    if (b.obs_signal.grow(n * cols, kFloor) || b.obs_ypred.grow(n * cols, kFloor) || b.obs_pll.grow(n * cols, kFloor) ||
+        b.obs_scales.grow(2 * n, kFloor) || b.obs_sq.grow(nq, kFloor) || b.obs_pq.grow(nq, kFloor) ||
+        b.obs_smean.grow(cols, kFloor) || b.obs_pmean.grow(cols, kFloor) || b.obs_waic.grow(4 * cols, kFloor) ||
+        b.obs_scount.grow(cols, kFloor) || b.obs_pcount.grow(cols, kFloor) || b.obs_wcount.grow(cols, kFloor))
+        return BCM3HIP_ERR_ALLOC;
+    for (hipEvent_t& e : b.obs_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    b.obs_timed = false;
+    hipStream_t s = c->stream;
+    HIPCHK(hipEventRecord(b.obs_ev[0], s));
+    int r = stage_batch(c, n, d, values);
+    if (r == 0) r = launch(c, n, c->values, c->logp, c->status, nullptr, nullptr, s);
+    if (r) return r;
+    double* const w = b.obs_waic;
+    HIPCHK(hipEventRecord(b.obs_ev[2], s));
+    hipError_t e = launch_ccm_predict(b.m, (int64_t)n, c->values, seed, b.m.T, b.obs_signal, b.obs_pll, b.obs_ypred,
+                                      b.obs_scales, nullptr, s);
+    HIPCHK(hipEventRecord(b.obs_ev[3], s));
+    if (e == hipSuccess)
+        e = launch_predict_quantiles((int64_t)n, (int64_t)cols, b.obs_signal, n_probs, pr, b.obs_sq, b.obs_smean,
+                                     b.obs_scount, s);
+    if (e == hipSuccess)
+        e = launch_predict_quantiles((int64_t)n, (int64_t)cols, b.obs_ypred, n_probs, pr, b.obs_pq, b.obs_pmean,
+                                     b.obs_pcount, s);
+    HIPCHK(hipEventRecord(b.obs_ev[4], s));
+    if (e == hipSuccess)
+        e = launch_predict_waic((int64_t)n, (int64_t)cols, b.obs_pll, b.obs_wcount, w, w + cols, w + 2 * cols, w + 3 * cols, s);
+    HIPCHK(hipEventRecord(b.obs_ev[5], s));
+    if (e != hipSuccess) {
+        fprintf(stderr, "bcm3hip: predictive-check kernel launch failed: %s\n", hipGetErrorString(e));
+        return BCM3HIP_ERR_HIP;
+    }
+    auto back = [&](void* dst, const void* src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    const size_t cb = cols * sizeof(double), ci = cols * sizeof(int32_t), full = n * cols * sizeof(double);
+    HIPCHK(back(logp, c->logp, n * sizeof(double)));
+    HIPCHK(back(status, c->status, n * sizeof(int32_t)));
+    HIPCHK(back(sig_q, b.obs_sq, nq * sizeof(double)));
+    HIPCHK(back(sig_mean, b.obs_smean, cb));
+    HIPCHK(back(sig_count, b.obs_scount, ci));
+    HIPCHK(back(pred_q, b.obs_pq, nq * sizeof(double)));
+    HIPCHK(back(pred_mean, b.obs_pmean, cb));
+    HIPCHK(back(pred_count, b.obs_pcount, ci));
+    HIPCHK(back(waic_count, b.obs_wcount, ci));
+    HIPCHK(back(lppd, w, cb));
+    HIPCHK(back(llh_mean, w + cols, cb));
+    HIPCHK(back(p_waic, w + 2 * cols, cb));
+    HIPCHK(back(elpd, w + 3 * cols, cb));
+    HIPCHK(back(signal, b.obs_signal, full));
+    HIPCHK(back(ypred, b.obs_ypred, full));
+    HIPCHK(back(pll, b.obs_pll, full));
+    HIPCHK(back(scales, b.obs_scales, 2 * n * sizeof(double)));
+    HIPCHK(hipEventRecord(b.obs_ev[1], s));
+    HIPCHK(hipStreamSynchronize(s));
+    b.obs_timed = true;
+    b.obs_rows = n;
+    return 0;
+}
+
+int bcm3hip_ccm_predict_obs_last_ms(bcm3hip_ctx* c, float* kernel_ms, float* quantile_ms, float* waic_ms, float* total_ms)
+{
+    if (!c || c->kind != Kind::Ccm || !c->ccm.obs_timed) return BCM3HIP_ERR_ARG;
+    auto& b = c->ccm;
+    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, b.obs_ev[2], b.obs_ev[3]));
+    if (quantile_ms) HIPCHK(hipEventElapsedTime(quantile_ms, b.obs_ev[3], b.obs_ev[4]));
+    if (waic_ms) HIPCHK(hipEventElapsedTime(waic_ms, b.obs_ev[4], b.obs_ev[5]));
+    if (total_ms) HIPCHK(hipEventElapsedTime(total_ms, b.obs_ev[0], b.obs_ev[1]));
+    return 0;
+}
+
+int bcm3hip_ccm_predict_obs_loo(bcm3hip_ctx* c, int32_t* count, int32_t* tail, double* pareto_k, double* elpd_loo,
+                                double* n_eff)
+{
+    if (!c || c->kind != Kind::Ccm || c->ccm.obs_rows == 0) return BCM3HIP_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    auto& b = c->ccm;
+    const size_t n = b.obs_rows, cols = (size_t)b.m.T;
+    if (b.loo_terms.grow(3 * cols, kFloor) || b.loo_count.grow(cols, kFloor) || b.loo_tail.grow(cols, kFloor))
+        return BCM3HIP_ERR_ALLOC;
+    for (hipEvent_t& e : b.loo_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    b.loo_timed = false;
+    double* const t = b.loo_terms;
+    HIPCHK(hipEventRecord(b.loo_ev[0], c->stream));
+    const hipError_t e = launch_psis_loo((int64_t)n, (int64_t)cols, b.obs_pll, b.loo_count, b.loo_tail, t, t + cols,
+                                         t + 2 * cols, c->stream);
+    if (e != hipSuccess) {
+        fprintf(stderr, "bcm3hip: PSIS-LOO kernel launch failed: %s\n", hipGetErrorString(e));
+        return BCM3HIP_ERR_HIP;
+    }
+    HIPCHK(hipEventRecord(b.loo_ev[1], c->stream));
+    auto back = [&](void* dst, const void* src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    const size_t cb = cols * sizeof(double), ci = cols * sizeof(int32_t);
+    HIPCHK(back(count, b.loo_count, ci));
+    HIPCHK(back(tail, b.loo_tail, ci));
+    HIPCHK(back(pareto_k, t, cb));
+    HIPCHK(back(elpd_loo, t + cols, cb));
+    HIPCHK(back(n_eff, t + 2 * cols, cb));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    b.loo_timed = true;
+    return 0;
+}
+
+int bcm3hip_ccm_predict_obs_loo_last_ms(bcm3hip_ctx* c, float* loo_ms)
+{
+    if (!c || c->kind != Kind::Ccm || !c->ccm.loo_timed) return BCM3HIP_ERR_ARG;
+    if (loo_ms) HIPCHK(hipEventElapsedTime(loo_ms, c->ccm.loo_ev[0], c->ccm.loo_ev[1]));
+    return 0;
+}
+
+int bcm3hip_ccm_predict_grid(bcm3hip_ctx* c, size_t n, size_t d, const double* values, int G, int n_probs,
+                             const double* probs, double* sig_q, double* sig_mean, int32_t* sig_count, double* event_q,
+                             double* event_mean, int32_t* event_count, double* logp, int32_t* status,
+                             double* signal_draws, double* event_draws)
+{
+    if (!c || c->kind != Kind::Ccm || (int)d != c->d || !values || !sig_q || !logp) return BCM3HIP_ERR_ARG;
+    PredictProbs pr{};
+    if (!predict_args_ok(n, n_probs, probs, pr)) return BCM3HIP_ERR_ARG;
+    if (G < 1 || G > BCM3HIP_CCM_GRID_MAX) return BCM3HIP_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    auto& b = c->ccm;
+    const size_t cols = (size_t)G, ecols = 3;
+    const size_t nq = (size_t)n_probs * cols, neq = (size_t)n_probs * ecols;
+    if (b.grid_signal.grow(n * cols, kFloor) || b.grid_events.grow(n * ecols, kFloor) || b.grid_sq.grow(nq, kFloor) ||
+        b.grid_smean.grow(cols, kFloor) || b.grid_scount.grow(cols, kFloor) || b.grid_eq.grow(neq, kFloor) ||
+        b.grid_emean.grow(ecols, kFloor) || b.grid_ecount.grow(ecols, kFloor))
+        return BCM3HIP_ERR_ALLOC;
+    for (hipEvent_t& e : b.grid_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    b.grid_timed = false;
+    hipStream_t s = c->stream;
+    HIPCHK(hipEventRecord(b.grid_ev[0], s));
+    int r = stage_batch(c, n, d, values);
+    if (r == 0) r = launch(c, n, c->values, c->logp, c->status, nullptr, nullptr, s);
+    if (r) return r;
+    HIPCHK(hipEventRecord(b.grid_ev[2], s));
+    hipError_t e = launch_ccm_predict(b.m, (int64_t)n, c->values, 0, G, b.grid_signal, nullptr, nullptr, nullptr,
+                                      b.grid_events, s);
+    HIPCHK(hipEventRecord(b.grid_ev[3], s));
+    if (e == hipSuccess)
+        e = launch_predict_quantiles((int64_t)n, (int64_t)cols, b.grid_signal, n_probs, pr, b.grid_sq, b.grid_smean,
+                                     b.grid_scount, s);
+    if (e == hipSuccess)
+        e = launch_predict_quantiles((int64_t)n, (int64_t)ecols, b.grid_events, n_probs, pr, b.grid_eq, b.grid_emean,
+                                     b.grid_ecount, s);
+    HIPCHK(hipEventRecord(b.grid_ev[4], s));
+    if (e != hipSuccess) {
+        fprintf(stderr, "bcm3hip: frame-grid kernel launch failed: %s\n", hipGetErrorString(e));
+        return BCM3HIP_ERR_HIP;
+    }
+    auto back = [&](void* dst, const void* src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    };
+    HIPCHK(back(logp, c->logp, n * sizeof(double)));
+    HIPCHK(back(status, c->status, n * sizeof(int32_t)));
+    HIPCHK(back(sig_q, b.grid_sq, nq * sizeof(double)));
+    HIPCHK(back(sig_mean, b.grid_smean, cols * sizeof(double)));
+    HIPCHK(back(sig_count, b.grid_scount, cols * sizeof(int32_t)));
+    HIPCHK(back(event_q, b.grid_eq, neq * sizeof(double)));
+    HIPCHK(back(event_mean, b.grid_emean, ecols * sizeof(double)));
+    HIPCHK(back(event_count, b.grid_ecount, ecols * sizeof(int32_t)));
+    HIPCHK(back(signal_draws, b.grid_signal, n * cols * sizeof(double)));
+    HIPCHK(back(event_draws, b.grid_events, n * ecols * sizeof(double)));
+    HIPCHK(hipEventRecord(b.grid_ev[1], s));
+    HIPCHK(hipStreamSynchronize(s));
+    b.grid_timed = true;
+    return 0;
+}
+
+int bcm3hip_ccm_predict_grid_last_ms(bcm3hip_ctx* c, float* kernel_ms, float* quantile_ms, float* total_ms)
+{
+    if (!c || c->kind != Kind::Ccm || !c->ccm.grid_timed) return BCM3HIP_ERR_ARG;
+    auto& b = c->ccm;
+    if (kernel_ms) HIPCHK(hipEventElapsedTime(kernel_ms, b.grid_ev[2], b.grid_ev[3]));
+    if (quantile_ms) HIPCHK(hipEventElapsedTime(quantile_ms, b.grid_ev[3], b.grid_ev[4]));
     if (total_ms) HIPCHK(hipEventElapsedTime(total_ms, b.grid_ev[0], b.grid_ev[1]));
     return 0;
 }

@@ -48,9 +48,9 @@ XM_FN double ccm_log_pdf_tnu4(double x, double mu, double sigma)
     return -0.9808292530117262 - 2.5 * xm::lib<false>::log1p(0.25 * xn * xn) - xm::lib<false>::log(sigma);
 }
 
-// the term of observation i (.cpp:73-86): strict comparisons of the index as a double, mitosis
-// first; sigma is taken as it comes (zero or negative included)
-XM_FN double ccm_term(const CcmParams& p, int i, double y)
+// the reporter signal of frame i (.cpp:73-82): strict comparisons of the index as a double, mitosis
+// first. Frames past the track are the same formula: a forecast.
+XM_FN double ccm_signal(const CcmParams& p, int i)
 {
     const double t = (double)i;
     double x = p.base_signal;
@@ -62,9 +62,21 @@ XM_FN double ccm_term(const CcmParams& p, int i, double y)
     } else if (t > p.S_entry_time) {
         x += p.S_signal_increase * (t - p.S_entry_time);
     }
+    return x;
+}
+
+// the error scale at signal x (.cpp:84); taken as it comes (zero or negative included)
+XM_FN double ccm_sigma(const CcmParams& p, double x)
+{
     const double xpos = (x < 0.0) ? 0.0 : x;  // std::max(x, 0.0)
-    const double sigma = p.additive_noise + p.proportional_noise * xpos;
-    return ccm_log_pdf_tnu4(y, x, sigma);
+    return p.additive_noise + p.proportional_noise * xpos;
+}
+
+// the term of observation i (.cpp:73-86)
+XM_FN double ccm_term(const CcmParams& p, int i, double y)
+{
+    const double x = ccm_signal(p, i);
+    return ccm_log_pdf_tnu4(y, x, ccm_sigma(p, x));
 }
 
 // logp += term, for cnt terms in index order

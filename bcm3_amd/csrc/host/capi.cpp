@@ -318,6 +318,88 @@ int bcm3_likelihood_expm_predict_last_ms(bcm3_likelihood* h, float* obs_ms /*[4]
     return 0;
 }
 
+// the cell_cycle_marker likelihood behind h with a device context, or null with the error logged
+static bcm3::LikelihoodGPUBase* ccm_likelihood(bcm3_likelihood* h, const char* what)
+{
+    bcm3::LikelihoodGPUBase* p = dynamic_cast<bcm3::LikelihoodCellCycleMarker*>(h->ll.get());
+    if (!p) {
+        LOGERROR("%s: a cell_cycle_marker likelihood is needed, this one is of type \"%s\"", what,
+                 h->ll->GetTypeName().c_str());
+        return nullptr;
+    }
+    if (!p->Context()) {
+        LOGERROR("%s: a device is needed; the likelihood was created without one", what);
+        return nullptr;
+    }
+    return p;
+}
+
+int bcm3_likelihood_ccm_predict_obs(bcm3_likelihood* h, size_t n, const double* values, uint64_t seed, int n_probs,
+                                    const double* probs, double* sig_q, double* sig_mean, int32_t* sig_count,
+                                    double* pred_q, double* pred_mean, int32_t* pred_count, int32_t* waic_count,
+                                    double* lppd, double* llh_mean, double* p_waic, double* elpd, double* logp,
+                                    int32_t* status, double* signal, double* ypred, double* pll, double* scales)
+{
+    if (!h || !h->ll) return -1;
+    bcm3::LikelihoodGPUBase* p = ccm_likelihood(h, "predicted measurements");
+    if (!p) return -2;
+    const int r = bcm3hip_ccm_predict_obs(p->Context(), n, p->GetNumVariables(), values, seed, n_probs, probs, sig_q,
+                                          sig_mean, sig_count, pred_q, pred_mean, pred_count, waic_count, lppd, llh_mean,
+                                          p_waic, elpd, logp, status, signal, ypred, pll, scales);
+    if (r) {
+        LOGERROR("bcm3hip_ccm_predict_obs: %s (at most %d parameter vectors and %d probabilities in [0, 1] per call)",
+                 bcm3hip_error_string(r), BCM3HIP_PREDICT_MAX_N, BCM3HIP_PREDICT_MAX_PROBS);
+        return -3;
+    }
+    return 0;
+}
+
+int bcm3_likelihood_ccm_predict_obs_loo(bcm3_likelihood* h, int32_t* count, int32_t* tail, double* pareto_k,
+                                        double* elpd_loo, double* n_eff, float* loo_ms)
+{
+    if (!h || !h->ll) return -1;
+    bcm3::LikelihoodGPUBase* p = ccm_likelihood(h, "PSIS-LOO");
+    if (!p) return -2;
+    int r = bcm3hip_ccm_predict_obs_loo(p->Context(), count, tail, pareto_k, elpd_loo, n_eff);
+    if (r == 0 && loo_ms) r = bcm3hip_ccm_predict_obs_loo_last_ms(p->Context(), loo_ms);
+    if (r) {
+        LOGERROR("bcm3hip_ccm_predict_obs_loo: %s (it takes the result of the likelihood's last ccm_predict_obs; an "
+                 "evaluation since then discards it)", bcm3hip_error_string(r));
+        return -3;
+    }
+    return 0;
+}
+
+int bcm3_likelihood_ccm_predict_grid(bcm3_likelihood* h, size_t n, const double* values, int G, int n_probs,
+                                     const double* probs, double* sig_q, double* sig_mean, int32_t* sig_count,
+                                     double* event_q, double* event_mean, int32_t* event_count, double* logp,
+                                     int32_t* status, double* signal_draws)
+{
+    if (!h || !h->ll) return -1;
+    bcm3::LikelihoodGPUBase* p = ccm_likelihood(h, "posterior predictive bands on a frame grid");
+    if (!p) return -2;
+    const int r = bcm3hip_ccm_predict_grid(p->Context(), n, p->GetNumVariables(), values, G, n_probs, probs, sig_q,
+                                           sig_mean, sig_count, event_q, event_mean, event_count, logp, status,
+                                           signal_draws, nullptr);
+    if (r) {
+        LOGERROR("bcm3hip_ccm_predict_grid: %s (at most %d parameter vectors, %d probabilities in [0, 1] and %d frames "
+                 "per call)", bcm3hip_error_string(r), BCM3HIP_PREDICT_MAX_N, BCM3HIP_PREDICT_MAX_PROBS,
+                 BCM3HIP_CCM_GRID_MAX);
+        return -3;
+    }
+    return 0;
+}
+
+int bcm3_likelihood_ccm_predict_last_ms(bcm3_likelihood* h, float* obs_ms /*[4]*/, float* grid_ms /*[3]*/)
+{
+    if (!h || !h->ll) return -1;
+    bcm3::LikelihoodGPUBase* p = ccm_likelihood(h, "predictive-check timings");
+    if (!p) return -2;
+    if (obs_ms && bcm3hip_ccm_predict_obs_last_ms(p->Context(), obs_ms, obs_ms + 1, obs_ms + 2, obs_ms + 3)) return -3;
+    if (grid_ms && bcm3hip_ccm_predict_grid_last_ms(p->Context(), grid_ms, grid_ms + 1, grid_ms + 2)) return -3;
+    return 0;
+}
+
 int64_t bcm3_likelihood_ccm_track(const bcm3_likelihood* h, double* data, int64_t cap, int32_t* track_ix)
 {
     if (!h || !h->ll) return -1;

@@ -41,6 +41,10 @@ def lib() -> C.CDLL:
     L.bcm3_likelihood_expm_predict_obs_loo.argtypes = [vp] * 6 + [C.POINTER(C.c_float)]
     L.bcm3_likelihood_expm_predict_grid.argtypes = [vp, sz, vp, C.c_int, vp, C.c_int, C.c_int, vp] + [vp] * 8
     L.bcm3_likelihood_expm_predict_last_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.bcm3_likelihood_ccm_predict_obs.argtypes = [vp, sz, vp, C.c_uint64, C.c_int, vp] + [vp] * 17
+    L.bcm3_likelihood_ccm_predict_obs_loo.argtypes = [vp] * 6 + [C.POINTER(C.c_float)]
+    L.bcm3_likelihood_ccm_predict_grid.argtypes = [vp, sz, vp, C.c_int, C.c_int, vp] + [vp] * 9
+    L.bcm3_likelihood_ccm_predict_last_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.bcm3_likelihood_ccm_track.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int32)]
     L.bcm3_likelihood_ccm_track.restype = C.c_int64
     L.bcm3_table_read.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_int64), vp, C.c_int64]
@@ -321,6 +325,72 @@ class Likelihood:
         out = np.empty(n)
         lib().bcm3_likelihood_ccm_track(self.h, out.ctypes.data, n, None)
         return ix.value, out
+
+    @property
+    def is_ccm(self) -> bool:
+        """cell_cycle_marker: the family bcm3_amd.predict serves through ccm_predict_*"""
+        if getattr(self, "_ccm_T", None) is None:
+            n = lib().bcm3_likelihood_ccm_track(self.h, None, 0, None)
+            self._ccm_T = int(n) if n >= 0 else False
+        return self._ccm_T is not False
+
+    def _ccm_frames(self) -> int:
+        return self._ccm_T if self.is_ccm else 0  # the library refuses other types itself
+
+    def ccm_predict_obs(self, values, probs, seed: int = 0, pointwise: bool = False) -> dict:
+        """cell_cycle_marker: predicted measurements of values [n, d] on the track's frames
+        (bcm3_likelihood_ccm_predict_obs; bcm3_amd.predict.measurements is the front end), the arrays of
+        _hip.Context.ccm_predict_obs."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        out = _hip.ccm_predict_obs_outputs(n, p.size, self._ccm_frames(), pointwise)
+        r = lib().bcm3_likelihood_ccm_predict_obs(self.h, n, v.ctypes.data, int(seed) & (2**64 - 1), p.size,
+                                                  p.ctypes.data, *_hip.predict_obs_pointers(out))
+        if r != 0:
+            _err("bcm3_likelihood_ccm_predict_obs", r)
+        return {k: a for k, a in out.items() if a is not None}
+
+    def ccm_predict_obs_loo(self) -> dict:
+        """the PSIS-LOO terms [T] of the last ccm_predict_obs (bcm3_likelihood_ccm_predict_obs_loo)"""
+        cols = self._ccm_frames()
+        out = {k: np.empty(cols, dtype=np.int32 if k in _hip.PSIS_INT_KEYS else np.float64) for k in _hip.PSIS_KEYS}
+        ms = C.c_float()
+        r = lib().bcm3_likelihood_ccm_predict_obs_loo(self.h, *(out[k].ctypes.data for k in _hip.PSIS_KEYS), C.byref(ms))
+        if r != 0:
+            _err("bcm3_likelihood_ccm_predict_obs_loo", r)
+        self._loo_ms = float(ms.value)
+        return out
+
+    def ccm_predict_grid(self, values, probs, frames=None, pointwise: bool = False) -> dict:
+        """cell_cycle_marker: the signal on frames 0 .. G-1 (G = frames, None: the track length) and the
+        event times (bcm3_likelihood_ccm_predict_grid; bcm3_amd.predict.posterior_predictive is the front
+        end), the arrays of _hip.Context.ccm_predict_grid (without the event draws)."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.d)
+        n = v.shape[0]
+        p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        G = int(self._ccm_frames() if frames is None else frames)
+        out = _hip.ccm_predict_grid_outputs(n, p.size, max(G, 0), pointwise, events=False)
+        r = lib().bcm3_likelihood_ccm_predict_grid(self.h, n, v.ctypes.data, G, p.size, p.ctypes.data,
+                                                   *_hip.predict_obs_pointers(out))
+        if r != 0:
+            _err("bcm3_likelihood_ccm_predict_grid", r)
+        out = {k: a for k, a in out.items() if a is not None}
+        out["frame"] = np.arange(G, dtype=np.float64)
+        return out
+
+    def ccm_predict_last_ms(self, which: str = "obs"):
+        """HIP-event ms of the last ccm_predict_obs ("obs": predict kernel, quantile launches, WAIC kernel,
+        whole call), ccm_predict_obs_loo ("loo": the PSIS-LOO kernel) or ccm_predict_grid ("grid": predict
+        kernel, quantile launches, whole call)"""
+        if which == "loo":
+            return (self.predict_obs_loo_last_ms(),)
+        ms = (C.c_float * 4)()
+        args = (ms, None) if which == "obs" else (None, ms)
+        r = lib().bcm3_likelihood_ccm_predict_last_ms(self.h, *args)
+        if r != 0:
+            _err("bcm3_likelihood_ccm_predict_last_ms", r)
+        return tuple(float(x) for x in ms)[:4 if which == "obs" else 3]
 
     def generated_code(self) -> str:
         """cell_population: the generated_derivative body this likelihood compiled (SBMLModel::GenerateCode)."""

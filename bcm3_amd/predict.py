@@ -6,7 +6,10 @@ The solve writes the trajectories of all draws into device memory, the quantile 
 host. For pop_pk_trajectory and pharmacokinetic_trajectory likelihoods, and for pharmaco_single and
 pharmaco_population (the matrix-exponential PK kernels; objects with a true `is_expm_pk`), whose
 observations lie on a flat axis [n_obs] with `patient` [n_obs] naming each one's patient and whose bands
-are drawn on a time grid (DESIGN.md §4 "predictive checks of the matrix-exponential PK family").
+are drawn on a time grid (DESIGN.md §4 "predictive checks of the matrix-exponential PK family"). And for
+cell_cycle_marker likelihoods (objects with a true `is_ccm`), whose axis is the frames of the one track
+and whose bands are those of the reporter signal (DESIGN.md §4 "predictive checks of the cell cycle
+marker").
 """
 from __future__ import annotations
 
@@ -58,7 +61,38 @@ def _expm_posterior_predictive(ll, v, p, times, states) -> dict:
     return out
 
 
-def posterior_predictive(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95), times=None, states: bool = False) -> dict:
+def _is_ccm(ll) -> bool:
+    """a cell_cycle_marker Likelihood or Context"""
+    return bool(getattr(ll, "is_ccm", False))
+
+
+def _ccm_posterior_predictive(ll, v, p, frames) -> dict:
+    G = _hip.ccm_frames_check(frames, ll.ccm_track()[1].size if frames is None else 0)  # before any device call
+    raw = ll.ccm_predict_grid(v, p, G)
+    return dict(signal=dict(quantiles=raw["sig_q"], mean=raw["sig_mean"], count=raw["sig_count"]),
+                events=dict(names=_hip.CCM_EVENTS, quantiles=raw["event_q"], mean=raw["event_mean"],
+                            count=raw["event_count"]),
+                frame=raw["frame"], time=raw["frame"], logp=raw["logp"], status=raw["status"])
+
+
+def _ccm_measurements(ll, v, p, seed, pointwise, loo, k_threshold) -> dict:
+    raw = ll.ccm_predict_obs(v, p, seed=seed, pointwise=pointwise)
+    observed = np.array(ll.ccm_track()[1], dtype=np.float64)
+    frame = np.arange(observed.size, dtype=np.float64)
+    out = dict(signal=dict(quantiles=raw["sig_q"], mean=raw["sig_mean"], count=raw["sig_count"]),
+               predicted=dict(quantiles=raw["pred_q"], mean=raw["pred_mean"], count=raw["pred_count"]),
+               observed=observed, frame=frame, time=frame, logp=raw["logp"], status=raw["status"])
+    order = np.argsort(p, kind="stable")
+    out["coverage"] = coverage(observed[None, :], raw["pred_q"][order[0]][None, :], raw["pred_q"][order[-1]][None, :])
+    _add_criteria(out, raw, ll.ccm_predict_obs_loo if loo else None, k_threshold)
+    if pointwise:
+        out.update(signal_draws=raw["signal"], predicted_draws=raw["ypred"], pointwise_llh=raw["pll"],
+                   scales=raw["scales"])
+    return out
+
+
+def posterior_predictive(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95), times=None, states: bool = False,
+                         frames=None) -> dict:
     """The bands of samples [n, d] (parameter vectors in the likelihood's variable order) under a
     bcm3_amd.likelihood.Likelihood or a PopPK bcm3_amd._hip.Context:
 
@@ -79,9 +113,24 @@ def posterior_predictive(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95)
                      compartment
       time [G], logp, status [n]
 
+    Under a cell_cycle_marker likelihood (or Context) the reporter signal is evaluated on `frames` frames
+    0 .. frames-1 (None: the track's length; at most 4096; beyond the track it is a forecast):
+
+      signal         dict(quantiles [len(probs), G], mean, count [G])
+      events         dict(names = ("S_entry", "plateau", "mitosis"), quantiles [len(probs), 3], mean, count
+                     [3]) of the three event times of every draw
+      frame [G] (also under time), logp, status [n]
+
     At most MAX_SAMPLES (8192) samples per call: more raises ValueError -- thin the draws first."""
     ll = likelihood_or_context
     v, p = _check(ll, samples, probs, "posterior_predictive")
+    if _is_ccm(ll):
+        if times is not None or states:
+            raise ValueError("times and states apply to pharmaco_single / pharmaco_population likelihoods only; a "
+                             "cell_cycle_marker likelihood takes frames")
+        return _ccm_posterior_predictive(ll, v, p, frames)
+    if frames is not None:
+        raise ValueError("frames applies to cell_cycle_marker likelihoods only")
     if _is_expm(ll):
         return _expm_posterior_predictive(ll, v, p, times, states)
     if times is not None or states:
@@ -221,6 +270,23 @@ def loo_totals(count, elpd_loo, lppd, pareto_k, k_threshold: float = 0.7) -> dic
                 n_high_k=int((np.asarray(pareto_k)[use] > k_threshold).sum()))
 
 
+def _add_criteria(out: dict, raw: dict, loo_call, k_threshold: float):
+    """out["waic"] from the WAIC arrays of a predict_obs result and, with loo_call (the likelihood's
+    *_predict_obs_loo, run on the pointwise log-likelihoods that result left on the device), out["loo"]"""
+    tot = waic_totals(raw["waic_count"], raw["lppd"], raw["p_waic"], raw["elpd"])
+    out["waic"] = dict(count=raw["waic_count"], lppd=raw["lppd"], mean=raw["llh_mean"], p_waic=raw["p_waic"],
+                       elpd=raw["elpd"], elpd_waic=tot["elpd_waic"], p_waic_total=tot["p_waic"],
+                       lppd_total=tot["lppd"], se=tot["se"], n_obs=tot["n_obs"])
+    if loo_call is not None:
+        t = loo_call()
+        with np.errstate(invalid="ignore"):
+            p_loo = raw["lppd"] - t["elpd_loo"]
+        tot = loo_totals(t["count"], t["elpd_loo"], raw["lppd"], t["pareto_k"], k_threshold)
+        out["loo"] = dict(count=t["count"], tail=t["tail"], pareto_k=t["pareto_k"], elpd=t["elpd_loo"], p_loo=p_loo,
+                          n_eff=t["n_eff"], elpd_loo=tot["elpd_loo"], p_loo_total=tot["p_loo"], se=tot["se"],
+                          n_obs=tot["n_obs"], n_high_k=tot["n_high_k"], k_threshold=float(k_threshold))
+
+
 def compare(a: dict, b: dict, criterion: str = "loo") -> dict:
     """The difference of two models' measurements results on the same data: elpd_diff = sum_i (a_i - b_i)
     of the pointwise elpd ("loo": out["loo"]["elpd"], "waic": out["waic"]["elpd"]) over the points both
@@ -271,9 +337,15 @@ def measurements(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95), seed: 
     patients' own observations concatenated in patient order: observed, time and patient [n_obs] say
     what, when and whose each column is, and coverage [P] is grouped by patient.
 
+    Under a cell_cycle_marker likelihood the axis is the track's frames [T]: `signal` (the reporter signal)
+    stands in place of `concentration` and signal_draws of concentration_draws, `frame` [T] = 0 .. T-1 is
+    also under `time`, and coverage has one element, the track's.
+
     At most MAX_SAMPLES (8192) samples per call: more raises ValueError -- thin the draws first."""
     ll = likelihood_or_context
     v, p = _check(ll, samples, probs, "measurements")
+    if _is_ccm(ll):
+        return _ccm_measurements(ll, v, p, seed, pointwise, loo, k_threshold)
     expm = _is_expm(ll)
     raw = ll.expm_predict_obs(v, p, seed=seed, pointwise=pointwise) if expm else ll.predict_obs(v, p, seed=seed,
                                                                                                  pointwise=pointwise)
@@ -290,18 +362,7 @@ def measurements(likelihood_or_context, samples, probs=(0.05, 0.5, 0.95), seed: 
                                               s["P"])
     else:
         out["coverage"] = coverage(observed, raw["pred_q"][order[0]], raw["pred_q"][order[-1]])
-    tot = waic_totals(raw["waic_count"], raw["lppd"], raw["p_waic"], raw["elpd"])
-    out["waic"] = dict(count=raw["waic_count"], lppd=raw["lppd"], mean=raw["llh_mean"], p_waic=raw["p_waic"],
-                       elpd=raw["elpd"], elpd_waic=tot["elpd_waic"], p_waic_total=tot["p_waic"],
-                       lppd_total=tot["lppd"], se=tot["se"], n_obs=tot["n_obs"])
-    if loo:  # on the pointwise log-likelihoods predict_obs left on the device
-        t = ll.expm_predict_obs_loo() if expm else ll.predict_obs_loo()
-        with np.errstate(invalid="ignore"):
-            p_loo = raw["lppd"] - t["elpd_loo"]
-        tot = loo_totals(t["count"], t["elpd_loo"], raw["lppd"], t["pareto_k"], k_threshold)
-        out["loo"] = dict(count=t["count"], tail=t["tail"], pareto_k=t["pareto_k"], elpd=t["elpd_loo"], p_loo=p_loo,
-                          n_eff=t["n_eff"], elpd_loo=tot["elpd_loo"], p_loo_total=tot["p_loo"], se=tot["se"],
-                          n_obs=tot["n_obs"], n_high_k=tot["n_high_k"], k_threshold=float(k_threshold))
+    _add_criteria(out, raw, (ll.expm_predict_obs_loo if expm else ll.predict_obs_loo) if loo else None, k_threshold)
     if pointwise:
         out.update(concentration_draws=raw["conc"], predicted_draws=raw["ypred"], pointwise_llh=raw["pll"],
                    scales=raw["scales"])

@@ -100,6 +100,27 @@ int bcm3_likelihood_expm_predict_grid(bcm3_likelihood* ll, size_t n, const doubl
  * launches, WAIC kernel, whole call) and last expm_predict_grid (grid_ms[4]: the grid's exponentials,
  * predict kernel, quantile launches, whole call); either may be NULL; -3 when that call has not run. */
 int bcm3_likelihood_expm_predict_last_ms(bcm3_likelihood* ll, float* obs_ms, float* grid_ms);
+/* The same checks for cell_cycle_marker (bcm3hip_ccm_predict_obs / _predict_obs_loo / _predict_grid on
+ * the likelihood's context; see bcm3hip.h for every array). The observation axis is the track's T
+ * frames (bcm3_likelihood_ccm_track). The grid call reduces the signal on frames 0 .. G-1 (G may exceed
+ * T) to sig_q[n_probs][G] and the three event times (S entry, plateau, mitosis) to event_q[n_probs][3];
+ * signal_draws[n][G] may be NULL. -2 for another likelihood type (the message names it) or a
+ * likelihood without a device, -3 when the device call fails. */
+int bcm3_likelihood_ccm_predict_obs(bcm3_likelihood* ll, size_t n, const double* values, uint64_t seed, int n_probs,
+                                    const double* probs, double* sig_q, double* sig_mean, int32_t* sig_count,
+                                    double* pred_q, double* pred_mean, int32_t* pred_count, int32_t* waic_count,
+                                    double* lppd, double* llh_mean, double* p_waic, double* elpd, double* logp,
+                                    int32_t* status, double* signal, double* ypred, double* pll, double* scales);
+int bcm3_likelihood_ccm_predict_obs_loo(bcm3_likelihood* ll, int32_t* count, int32_t* tail, double* pareto_k,
+                                        double* elpd_loo, double* n_eff, float* loo_ms);
+int bcm3_likelihood_ccm_predict_grid(bcm3_likelihood* ll, size_t n, const double* values, int G, int n_probs,
+                                     const double* probs, double* sig_q, double* sig_mean, int32_t* sig_count,
+                                     double* event_q, double* event_mean, int32_t* event_count, double* logp,
+                                     int32_t* status, double* signal_draws);
+/* HIP-event times in ms of the likelihood's last ccm_predict_obs (obs_ms[4]: predict kernel, quantile
+ * launches, WAIC kernel, whole call) and last ccm_predict_grid (grid_ms[3]: predict kernel, quantile
+ * launches, whole call); either may be NULL; -3 when that call has not run. */
+int bcm3_likelihood_ccm_predict_last_ms(bcm3_likelihood* ll, float* obs_ms, float* grid_ms);
 /* cell_cycle_marker: the track the likelihood evaluates against (the row ccm.track_ix selected):
  * copies up to cap frames into data (may be NULL) and the row index into *track_ix (may be NULL);
  * returns the number of frames, -2 for other likelihood types. */

@@ -1123,6 +1123,59 @@ int bcm3hip_expm_predict_grid(bcm3hip_ctx* ctx, size_t n, size_t d, const double
 int bcm3hip_expm_predict_grid_last_ms(bcm3hip_ctx* ctx, float* exp_ms, float* kernel_ms, float* quantile_ms,
                                       float* total_ms);
 
+/* ---- Predictive checks of the cell_cycle_marker likelihood (ccm_kernel.hip) ----
+ * cell_cycle_marker contexts (bcm3hip_open_cell_cycle_marker); every other kind is BCM3HIP_ERR_ARG
+ * before any launch. The observation axis is the track's T frames; the signal may be asked for on
+ * frames 0 .. G-1 with G beyond T (a forecast), 1 <= G <= BCM3HIP_CCM_GRID_MAX. */
+#define BCM3HIP_CCM_GRID_MAX 4096
+/* What the predict kernel leaves per draw e of values[n][10], from the kernel's source compiled for
+ * the host (needs no device; bit-identical to the kernel). Any output may be NULL, pll and ypred both
+ * or neither:
+ *   signal[n][G] the reporter signal x of frames 0 .. G-1
+ *   pll[n][T]    the term the likelihood adds for the frame, bit for bit; NaN ("no value") where the
+ *                frame is not observed (the likelihood adds exactly 0 there). A term that is NaN
+ *                (sigma <= 0) is the quiet NaN 0x7ff8000000000000; an infinite one stays
+ *   ypred[n][T]  x + sigma * tau(seed, e, 0, i), sigma = additive + proportional * max(x, 0), tau the
+ *                variate of bcm3hip_t4_draws_host(seed, n, 1, T); NaN where x or sigma is not finite
+ *   scales[n][2] (additive_noise, proportional_noise)
+ *   events[n][3] (S_entry_time, plateau_time, mitosis_time) as the likelihood forms them
+ * BCM3HIP_ERR_ARG for a NULL model or values, T < 1, n < 0 or G outside its limits. */
+int bcm3hip_ccm_predict_host(const bcm3hip_ccm_model* model, int64_t n, const double* values, uint64_t seed, int G,
+                             double* signal, double* pll, double* ypred, double* scales, double* events);
+/* bcm3hip_predict_obs for these contexts on the frame axis [T]: the ordinary launch for logp / status,
+ * the predict kernel with G = T, then the bands of signal and ypred (bcm3hip_column_quantiles) and the
+ * WAIC terms of pll (bcm3hip_column_waic), all on the context's stream. Copies back sig_q / pred_q
+ * [n_probs][T], their mean and count [T] (may be NULL), the five WAIC arrays [T] (may be NULL), logp[n]
+ * and status[n] (may be NULL); signal, ypred, pll [n][T] and scales [n][2] only where the pointer is not
+ * NULL. d must be 10; limits on n and probs as bcm3hip_predict_obs. Synchronous. */
+int bcm3hip_ccm_predict_obs(bcm3hip_ctx* ctx, size_t n, size_t d, const double* values, uint64_t seed, int n_probs,
+                            const double* probs, double* sig_q, double* sig_mean, int32_t* sig_count, double* pred_q,
+                            double* pred_mean, int32_t* pred_count, int32_t* waic_count, double* lppd, double* llh_mean,
+                            double* p_waic, double* elpd, double* logp, int32_t* status, double* signal, double* ypred,
+                            double* pll, double* scales);
+/* HIP-event times of the context's last bcm3hip_ccm_predict_obs (any may be NULL): the predict kernel,
+ * the two quantile launches, the WAIC kernel, the whole call. */
+int bcm3hip_ccm_predict_obs_last_ms(bcm3hip_ctx* ctx, float* kernel_ms, float* quantile_ms, float* waic_ms,
+                                    float* total_ms);
+/* bcm3hip_column_psis_loo over the pll[n][T] the context's last bcm3hip_ccm_predict_obs left on the
+ * device; the five arrays [T] (any may be NULL). BCM3HIP_ERR_ARG when no such result is current: before
+ * the first one, and after any later evaluation or predictive call on the context. */
+int bcm3hip_ccm_predict_obs_loo(bcm3hip_ctx* ctx, int32_t* count, int32_t* tail, double* pareto_k, double* elpd_loo,
+                                double* n_eff);
+int bcm3hip_ccm_predict_obs_loo_last_ms(bcm3hip_ctx* ctx, float* loo_ms);
+/* Bands of the signal on frames 0 .. G-1 and of the three event times: sig_q[n_probs][G], sig_mean /
+ * sig_count [G] (may be NULL); event_q[n_probs][3], event_mean / event_count [3] (S entry, plateau,
+ * mitosis; may be NULL), by the quantile kernel on the events[n][3] the predict kernel fills; logp[n]
+ * and status[n] (may be NULL) of the ordinary launch. signal_draws[n][G] and event_draws[n][3] (NULL
+ * unless wanted) are the draws themselves. Synchronous. */
+int bcm3hip_ccm_predict_grid(bcm3hip_ctx* ctx, size_t n, size_t d, const double* values, int G, int n_probs,
+                             const double* probs, double* sig_q, double* sig_mean, int32_t* sig_count, double* event_q,
+                             double* event_mean, int32_t* event_count, double* logp, int32_t* status,
+                             double* signal_draws, double* event_draws);
+/* HIP-event times of the context's last bcm3hip_ccm_predict_grid (any may be NULL): the predict kernel,
+ * the two quantile launches, the whole call. */
+int bcm3hip_ccm_predict_grid_last_ms(bcm3hip_ctx* ctx, float* kernel_ms, float* quantile_ms, float* total_ms);
+
 #ifdef __cplusplus
 }
 #endif
